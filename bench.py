@@ -8,8 +8,13 @@ already resident in HBM.  N=1 workload: BASELINE.json configs[3]'s 16M-particle 
 (n3=252 -> 16,003,008 particles) on one GPU; N>1: the same total problem partitioned into
 spatial slabs (strong scaling), see dieselfluid_amd/slab.py.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times K steps and prints the headline (`value`, `ms_per_step`); N>1 adds the slab
+exchange's status words, which void the run when they are not zero.  `--dump-outputs DIR` writes the particle state
+after the last timed step (dump_outputs).  Everything else is measured only with `--full`:
   roofline     -- dominant kernel: algorithmic bytes per launch / HIP-event duration
+  kernels_ms   -- per-kernel times from a 10-step segment after the timed region
+  exact / developed / drifted -- the same scene in DSL_MATH_EXACT, after the flow has developed, the PCISPH
+                  predictor after it has drifted
   cpu_baseline -- the CPU oracle (a port of the reference's single-threaded Go path)
                   timed on a bounded sample of the same workload, rank 0, N=1 only
 """
@@ -28,6 +33,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICRO
 #   force+integrate: read x,v,rho (28), write x,v (24)        [SURVEY 8d: 52 B]
 BYTES_DENSITY = 16
 BYTES_FORCE = 52
+# --dump-outputs: at most this many particles (28 B each: 58.7 MB), above it a sample drawn with DUMP_SEED
+DUMP_MAX_PARTICLES = 1 << 21
+DUMP_SEED = 20261016
 
 
 def parse():
@@ -47,24 +55,36 @@ def parse():
                          "particle has moved skin h / 2 (0 = sort and sweep every step; default: the library's own default)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a library option for A/B runs (include/dslsph.h DSL_OPT_*, e.g. pci_qincr=0); N=1 only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: HIP events around the dominant kernels in the "
+                         "timed region, per-kernel times, roofline, the exact / developed / drifted segments and the CPU "
+                         "baseline (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps write positions, velocities and densities as float32 DIR/<name>.npy "
+                         f"(every particle, or a fixed seeded sample of {DUMP_MAX_PARTICLES} above that many)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="N>1: exchange after the whole force pass")
     ap.add_argument("--developed-steps", type=int, default=10000,
-                    help="N=1 WCSPH only: after the timed region advance this many steps (the column collapses, the "
+                    help="--full, N=1 WCSPH only: after the timed region advance this many steps (the column collapses, the "
                          "lattice melts: ~10000 steps = 0.45 s of flow at n3=252) and time 20 more; reported as "
                          "developed_ms_per_step beside the headline.  0 = skip")
     ap.add_argument("--drift-steps", type=int, default=400,
-                    help="N=1 --method pcisph only: after the timed region advance this many steps -- the reference never "
+                    help="--full, N=1 --method pcisph only: after the timed region advance this many steps -- the reference never "
                          "re-synchronises its predictor (pcisph_darwin.go:28-41), so DensityF's query points leave their "
                          "particles and the library sorts them into cells of their own (dsl_pcisph_set_binning) -- and time "
                          "20 more; reported under `drifted` beside the line.  0 = skip")
     ap.add_argument("--exact-steps", type=int, default=5,
-                    help="N=1 WCSPH, --math fast only: also time this many steps of the SAME scene in DSL_MATH_EXACT (the "
+                    help="--full, N=1 WCSPH, --math fast only: also time this many steps of the SAME scene in DSL_MATH_EXACT (the "
                          "mode that is bit for bit the oracle's) on a second engine; reported under `exact`.  0 = skip")
     ap.add_argument("--cpu-n3", type=int, default=100,
-                    help="edge of the CPU-baseline sample block (100 = BASELINE configs[1]'s 1M particles)")
-    ap.add_argument("--cpu-steps", type=int, default=1)
-    return ap.parse_args()
+                    help="--full: edge of the CPU-baseline sample block (100 = BASELINE configs[1]'s 1M particles)")
+    ap.add_argument("--cpu-steps", type=int, default=1, help="--full: CPU-baseline steps")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: N=1 only")
+    return args
 
 
 def cpu_baseline(args):
@@ -91,6 +111,21 @@ def cpu_baseline(args):
         "sample": f"same dam-break scene at n3={n3} ({n3**3} particles), {args.cpu_steps} WCSPH step(s), "
                   f"{dt:.1f} s of CPU; oracle/dsl_oracle.c single thread",
     }
+
+
+def dump_outputs(directory, eng):
+    """What a caller of the stepping path receives after the last timed step -- positions, velocities, densities in
+    particle order -- as float32 <directory>/<name>.npy.  Above DUMP_MAX_PARTICLES every array keeps the same rows: a
+    sample drawn with DUMP_SEED, in ascending particle order, so that two builds compare output for output."""
+    import numpy as np
+    out = {name: eng.download(name) for name in ("positions", "velocities", "densities")}
+    n = out["densities"].shape[0]
+    if n > DUMP_MAX_PARTICLES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_PARTICLES, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def launch_ranks(args):
@@ -239,44 +274,49 @@ def main():
         torch.cuda.synchronize()
 
     # Per-kernel HIP events bracket launches: around every kernel they cost 1.8 % of the 2.5 ms step
-    # at N=1 and about 10 % of a slab rank's 0.5 ms step.  N=1 therefore times only the two dominant
+    # at N=1 and about 10 % of a slab rank's 0.5 ms step.  --full, N=1 therefore times only the two dominant
     # kernels (the roofline's) inside the timed region and the rest in a short segment after it;
-    # N>1 times everything in that segment, `value` is measured without any.
-    events_in_region = world == 1
+    # N>1 times everything in that segment, `value` is measured without any.  A plain run records no events.
+    events_in_region = world == 1 and args.full
     if world > 1:
         dog.arm(limit, "warm-up steps (first halo exchange)")
     step(args.warmup)
-    for e in engines:
-        e.timing_reset()
-        e.timing_enable(2 if events_in_region else 0)
+    if args.full:
+        for e in engines:
+            e.timing_reset()
+            e.timing_enable(2 if events_in_region else 0)
     barrier()
     if world > 1:
         dog.arm(limit, "timed steps")
-    skin0 = (engines[0].get_option("skin_steps"), engines[0].get_option("skin_rebuilds")) if world == 1 else (0, 0)
+    skin0 = (engines[0].get_option("skin_steps"), engines[0].get_option("skin_rebuilds")) if world == 1 and args.full else (0, 0)
     t0 = time.perf_counter()
     step(args.steps)
     barrier()
     dt = time.perf_counter() - t0
-    skin1 = (engines[0].get_option("skin_steps"), engines[0].get_option("skin_rebuilds")) if world == 1 else (0, 0)
-    skin_fields = (engines[0].get_option("skin_fields_own"), engines[0].get_option("skin_fields_padded")) if world == 1 else (0, 0)
-    def opt_or(name, default=0.0):  # (an older build loaded through DSL_LIB for an A/B run may not know the option)
-        try:
-            return engines[0].get_option(name)
-        except Exception:
-            return default
-    skin_tau = opt_or("skin_tau_steps") if world == 1 else 0.0
+    if args.dump_outputs:  # (before anything else runs on the engine: the state the timed steps left)
+        dump_outputs(args.dump_outputs, engines[0])
+    if args.full:
+        skin1 = (engines[0].get_option("skin_steps"), engines[0].get_option("skin_rebuilds")) if world == 1 else (0, 0)
+        skin_fields = (engines[0].get_option("skin_fields_own"), engines[0].get_option("skin_fields_padded")) if world == 1 else (0, 0)
+        def opt_or(name, default=0.0):  # (an older build loaded through DSL_LIB for an A/B run may not know the option)
+            try:
+                return engines[0].get_option(name)
+            except Exception:
+                return default
+        skin_tau = opt_or("skin_tau_steps") if world == 1 else 0.0
+        if world > 1:
+            dog.arm(limit, "per-kernel timing segment")
+        hot = {k: engines[0].timing(k) for k in ("density", "force_integrate", "pci_density")}
+        timed_launch_steps = min(args.steps, 10)
+        for e in engines:
+            e.timing_reset()
+            e.timing_enable(True)
+        step(timed_launch_steps)
+        barrier()
+        for e in engines:
+            e.timing_enable(False)
     if world > 1:
-        dog.arm(limit, "per-kernel timing segment and the closing reductions")
-    hot = {k: engines[0].timing(k) for k in ("density", "force_integrate", "pci_density")}
-    timed_launch_steps = min(args.steps, 10)
-    for e in engines:
-        e.timing_reset()
-        e.timing_enable(True)
-    step(timed_launch_steps)
-    barrier()
-    for e in engines:
-        e.timing_enable(False)
-    if world > 1:
+        dog.arm(limit, "the closing reductions")
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
@@ -300,135 +340,183 @@ def main():
                           device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(ov, op=dist.ReduceOp.MAX)
         overflow, band_missed, query_escaped = int(ov[0].item()), int(ov[1].item()), int(ov[2].item())
-    def timing_of(k):  # N=1: the dominant kernels as timed inside the timed region
-        return hot[k] if events_in_region and k in hot else eng.timing(k)
-
-    ms_d, n_d = timing_of("density")
-    ms_f, n_f = timing_of("force_integrate")
-    steps_f = args.steps if events_in_region else timed_launch_steps
-    if n_f > steps_f:  # split force pass: two launches per step, quote the pass
-        ms_f = ms_f * n_f / steps_f
-    # particles this rank integrates (ghosts take part in the sums but are not integrated)
-    n_local = eng.n if world == 1 else eng.n_owned()
-    n_live = eng.n
     if overflow or band_missed:
         sys.stderr.write(f"bench.py: slab exchange overflow={overflow} band_missed={band_missed}: particles or ghosts "
                          "were lost, the measurement is void\n")
         if world > 1:
             dist.destroy_process_group()
         raise SystemExit(3)
-    if args.method == "pcisph":
-        ms_f = timing_of("pci_density")[0]  # dominant PCISPH kernel: predicted density, 20 B/particle
-        kname, kms, kbytes = "k_pci_density", ms_f, 20
-    elif ms_f >= ms_d:
-        kname, kms, kbytes = "k_force_integrate", ms_f, BYTES_FORCE
-    else:
-        kname, kms, kbytes = "k_density", ms_d, BYTES_DENSITY
-    if world == 1 and args.method == "wcsph" and skin1[0] > skin0[0]:  # the timed steps walked neighbour lists
-        kname = {"k_force_integrate": "k_force_list", "k_density": "k_density_list"}[kname]
-    achieved = n_local * kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
-    st = eng.stats()
-    kernels_ms = {k: round(timing_of(k)[0], 4) for k in
-                  (("cell_rank", "scan", "scatter", "tile_list", "neigh_lists", "density", "force_integrate")
-                   if args.method == "wcsph" else
-                   ("cell_rank", "scan", "scatter", "tile_list", "density", "viscous", "gradient",
-                    "pci_predict", "pci_density", "update"))}
-    exact = None
-    if world == 1 and args.method == "wcsph" and args.math == "fast" and args.exact_steps > 0:
-        # the same scene on a second engine in DSL_MATH_EXACT: the reference's own float32 operations in the
-        # reference's order (every EXACT parity test is array_equal against the oracle), driver-reproducible
-        for e in engines:
-            e.timing_enable(False)
-        pe, pos_e = scenes.dambreak_scene(n3, math_mode=0)
-        xe = SPHEngine(pe, device=local_rank)
-        xe.upload("positions", pos_e)
-        xe.reset_forces()
-        del pos_e
-        xe.wcsph_step(2)
-        xe.timing_reset()
-        xe.timing_enable(2)
-        torch.cuda.synchronize()
-        te = time.perf_counter()
-        xe.wcsph_step(args.exact_steps)
-        torch.cuda.synchronize()
-        te = (time.perf_counter() - te) / args.exact_steps
-        exact = {"value": round(n_total / te / 1e6, 3), "ms_per_step": round(te * 1e3, 4), "steps": args.exact_steps,
-                 "warmup": 2, "kernels_ms": {k: round(xe.timing(k)[0], 4) for k in ("density", "force_integrate")},
-                 "math": "exact (bit for bit the CPU oracle's results; tests/test_gpu_parity.py)"}
-        xe.close()
-        del xe
-    developed = None
-    if world == 1 and args.method == "wcsph" and args.developed_steps > 0:
-        # the headline above is the contract's configuration (the jittered lattice: exactly 8 per cell);
-        # this is the same engine once the flow has developed
-        for e in engines:
-            e.timing_enable(False)
-        chunk = 500
-        for _ in range(args.developed_steps // chunk):
-            step(chunk)
-        torch.cuda.synchronize()
-        td = time.perf_counter()
-        step(20)
-        torch.cuda.synchronize()
-        td = (time.perf_counter() - td) / 20
-        eng.timing_reset()
-        eng.timing_enable(True)
-        step(5)
-        dk = {k: round(eng.timing(k)[0], 4) for k in ("cell_rank", "scan", "scatter", "tile_list", "neigh_lists", "density", "force_integrate")}
-        eng.timing_enable(False)
-        sd = eng.stats()
-        developed = {"ms_per_step": round(td * 1e3, 4), "value": round(n_total / td / 1e6, 3), "kernels_ms": dk,
-                     "after_steps": args.warmup + args.steps + timed_launch_steps + (args.developed_steps // chunk) * chunk,
-                     "max_cell_count": sd.max_cell_count, "max_vel": sd.max_vel}
-    drifted = None
-    if world == 1 and args.method == "pcisph" and args.drift_steps > 0:
-        for e in engines:
-            e.timing_enable(False)
-        step(args.drift_steps)
-        torch.cuda.synchronize()
-        td = time.perf_counter()
-        step(20)
-        torch.cuda.synchronize()
-        td = (time.perf_counter() - td) / 20
-        eng.timing_reset()
-        eng.timing_enable(True)
-        step(5)
-        dk = {k: round(eng.timing(k)[0], 4) for k in ("cell_rank", "scan", "scatter", "tile_list", "density", "viscous",
-                                                      "pci_predict", "pci_density", "update")}
-        eng.timing_enable(False)
-        drifted = {"ms_per_step": round(td * 1e3, 4), "value": round(n_total / td / 1e6, 3), "kernels_ms": dk,
-                   "after_steps": args.warmup + args.steps + timed_launch_steps + args.drift_steps,
-                   "queries_binned": bool(eng.pcisph_binning()[1]),
-                   "note": "pci_predict = predict + the queries' counting sort + query-tile tables, pci_density = the sweep; "
-                           "per correction iteration"}
-    # HBM bytes per launch and the vector-ALU counters cannot be sampled from inside this process; they come from the
-    # committed rocprofv3 --pmc passes of this same command (profiles/traffic.json, written by tools/make_traffic.py from
-    # the round's final profile) and are only quoted for the configuration and the kernel they were measured on.
-    traffic = valu = None
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-        if world == 1 and tj.get("particles") == n_total and args.math == "fast" and kname in tj:
-            traffic = tj[kname]["bytes"]
-            valu = {"insts_per_launch": tj[kname]["insts_valu"], "issue_frac": tj[kname]["valu_issue_frac"],
-                    "busy_frac": tj[kname]["valu_busy_frac"],
-                    "definition": "issue_frac = SQ_INSTS_VALU x 2 / (1024 SIMDs x clocks), busy_frac = SQ_ACTIVE_INST_VALU x 4 / "
-                                  "(1024 SIMDs x clocks); " + tj.get("source", "")}
-    except Exception:
+    if args.full:
+        def timing_of(k):  # N=1: the dominant kernels as timed inside the timed region
+            return hot[k] if events_in_region and k in hot else eng.timing(k)
+
+        ms_d, n_d = timing_of("density")
+        ms_f, n_f = timing_of("force_integrate")
+        steps_f = args.steps if events_in_region else timed_launch_steps
+        if n_f > steps_f:  # split force pass: two launches per step, quote the pass
+            ms_f = ms_f * n_f / steps_f
+        # particles this rank integrates (ghosts take part in the sums but are not integrated)
+        n_local = eng.n if world == 1 else eng.n_owned()
+        n_live = eng.n
+        if args.method == "pcisph":
+            ms_f = timing_of("pci_density")[0]  # dominant PCISPH kernel: predicted density, 20 B/particle
+            kname, kms, kbytes = "k_pci_density", ms_f, 20
+        elif ms_f >= ms_d:
+            kname, kms, kbytes = "k_force_integrate", ms_f, BYTES_FORCE
+        else:
+            kname, kms, kbytes = "k_density", ms_d, BYTES_DENSITY
+        if world == 1 and args.method == "wcsph" and skin1[0] > skin0[0]:  # the timed steps walked neighbour lists
+            kname = {"k_force_integrate": "k_force_list", "k_density": "k_density_list"}[kname]
+        achieved = n_local * kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+        st = eng.stats()
+        kernels_ms = {k: round(timing_of(k)[0], 4) for k in
+                      (("cell_rank", "scan", "scatter", "tile_list", "neigh_lists", "density", "force_integrate")
+                       if args.method == "wcsph" else
+                       ("cell_rank", "scan", "scatter", "tile_list", "density", "viscous", "gradient",
+                        "pci_predict", "pci_density", "update"))}
+        exact = None
+        if world == 1 and args.method == "wcsph" and args.math == "fast" and args.exact_steps > 0:
+            # the same scene on a second engine in DSL_MATH_EXACT: the reference's own float32 operations in the
+            # reference's order (every EXACT parity test is array_equal against the oracle), driver-reproducible
+            for e in engines:
+                e.timing_enable(False)
+            pe, pos_e = scenes.dambreak_scene(n3, math_mode=0)
+            xe = SPHEngine(pe, device=local_rank)
+            xe.upload("positions", pos_e)
+            xe.reset_forces()
+            del pos_e
+            xe.wcsph_step(2)
+            xe.timing_reset()
+            xe.timing_enable(2)
+            torch.cuda.synchronize()
+            te = time.perf_counter()
+            xe.wcsph_step(args.exact_steps)
+            torch.cuda.synchronize()
+            te = (time.perf_counter() - te) / args.exact_steps
+            exact = {"value": round(n_total / te / 1e6, 3), "ms_per_step": round(te * 1e3, 4), "steps": args.exact_steps,
+                     "warmup": 2, "kernels_ms": {k: round(xe.timing(k)[0], 4) for k in ("density", "force_integrate")},
+                     "math": "exact (bit for bit the CPU oracle's results; tests/test_gpu_parity.py)"}
+            xe.close()
+            del xe
+        developed = None
+        if world == 1 and args.method == "wcsph" and args.developed_steps > 0:
+            # the headline above is the contract's configuration (the jittered lattice: exactly 8 per cell);
+            # this is the same engine once the flow has developed
+            for e in engines:
+                e.timing_enable(False)
+            chunk = 500
+            for _ in range(args.developed_steps // chunk):
+                step(chunk)
+            torch.cuda.synchronize()
+            td = time.perf_counter()
+            step(20)
+            torch.cuda.synchronize()
+            td = (time.perf_counter() - td) / 20
+            eng.timing_reset()
+            eng.timing_enable(True)
+            step(5)
+            dk = {k: round(eng.timing(k)[0], 4) for k in ("cell_rank", "scan", "scatter", "tile_list", "neigh_lists", "density", "force_integrate")}
+            eng.timing_enable(False)
+            sd = eng.stats()
+            developed = {"ms_per_step": round(td * 1e3, 4), "value": round(n_total / td / 1e6, 3), "kernels_ms": dk,
+                         "after_steps": args.warmup + args.steps + timed_launch_steps + (args.developed_steps // chunk) * chunk,
+                         "max_cell_count": sd.max_cell_count, "max_vel": sd.max_vel}
+        drifted = None
+        if world == 1 and args.method == "pcisph" and args.drift_steps > 0:
+            for e in engines:
+                e.timing_enable(False)
+            step(args.drift_steps)
+            torch.cuda.synchronize()
+            td = time.perf_counter()
+            step(20)
+            torch.cuda.synchronize()
+            td = (time.perf_counter() - td) / 20
+            eng.timing_reset()
+            eng.timing_enable(True)
+            step(5)
+            dk = {k: round(eng.timing(k)[0], 4) for k in ("cell_rank", "scan", "scatter", "tile_list", "density", "viscous",
+                                                          "pci_predict", "pci_density", "update")}
+            eng.timing_enable(False)
+            drifted = {"ms_per_step": round(td * 1e3, 4), "value": round(n_total / td / 1e6, 3), "kernels_ms": dk,
+                       "after_steps": args.warmup + args.steps + timed_launch_steps + args.drift_steps,
+                       "queries_binned": bool(eng.pcisph_binning()[1]),
+                       "note": "pci_predict = predict + the queries' counting sort + query-tile tables, pci_density = the sweep; "
+                               "per correction iteration"}
+        # HBM bytes per launch and the vector-ALU counters cannot be sampled from inside this process; they come from the
+        # committed rocprofv3 --pmc passes of this same command (profiles/traffic.json, written by tools/make_traffic.py from
+        # the round's final profile) and are only quoted for the configuration and the kernel they were measured on.
         traffic = valu = None
-    # the density + force PASS in real traffic: both kernels' counter bytes over both kernels' time
-    pass_traffic_frac = None
-    try:
-        kd, kf = ("k_density_list", "k_force_list") if kname.endswith("_list") else ("k_density", "k_force_integrate")
-        if traffic is not None and kd in tj and kf in tj and (ms_d + ms_f) > 0:
-            pass_traffic_frac = (tj[kd]["bytes"] + tj[kf]["bytes"]) / ((ms_d + ms_f) * 1e-3) / 1e9 / HBM_PEAK_GBS
-    except Exception:
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+            if world == 1 and tj.get("particles") == n_total and args.math == "fast" and kname in tj:
+                traffic = tj[kname]["bytes"]
+                valu = {"insts_per_launch": tj[kname]["insts_valu"], "issue_frac": tj[kname]["valu_issue_frac"],
+                        "busy_frac": tj[kname]["valu_busy_frac"],
+                        "definition": "issue_frac = SQ_INSTS_VALU x 2 / (1024 SIMDs x clocks), busy_frac = SQ_ACTIVE_INST_VALU x 4 / "
+                                      "(1024 SIMDs x clocks); " + tj.get("source", "")}
+        except Exception:
+            traffic = valu = None
+        # the density + force PASS in real traffic: both kernels' counter bytes over both kernels' time
         pass_traffic_frac = None
-    hbm_frac = achieved / HBM_PEAK_GBS
-    # the roof that binds: the kernel's real HBM traffic against the peak, or the vector ALUs' busy share
-    real_hbm_frac = (traffic / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and kms > 0) else None
-    bound = "hbm"
-    if valu is not None and valu["busy_frac"] > max(hbm_frac, real_hbm_frac or 0.0):
-        bound = "valu"
+        try:
+            kd, kf = ("k_density_list", "k_force_list") if kname.endswith("_list") else ("k_density", "k_force_integrate")
+            if traffic is not None and kd in tj and kf in tj and (ms_d + ms_f) > 0:
+                pass_traffic_frac = (tj[kd]["bytes"] + tj[kf]["bytes"]) / ((ms_d + ms_f) * 1e-3) / 1e9 / HBM_PEAK_GBS
+        except Exception:
+            pass_traffic_frac = None
+        hbm_frac = achieved / HBM_PEAK_GBS
+        # the roof that binds: the kernel's real HBM traffic against the peak, or the vector ALUs' busy share
+        real_hbm_frac = (traffic / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and kms > 0) else None
+        bound = "hbm"
+        if valu is not None and valu["busy_frac"] > max(hbm_frac, real_hbm_frac or 0.0):
+            bound = "valu"
+        full = {
+            "roofline": {
+                "bound": bound,
+                "kernel": kname,
+                "achieved": round(achieved, 2),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": traffic,
+                "traffic_ratio": round(traffic / (n_local * kbytes), 3) if traffic else None,
+                "traffic_frac_of_peak": round(real_hbm_frac, 4) if real_hbm_frac else None,
+                "valu": valu,
+                "avg_ms": round(kms, 4),
+                "bytes_per_particle": kbytes,
+                "pass_density_ms": round(ms_d, 4),
+                "pass_force_ms": round(ms_f, 4),
+                "pass_frac_68B": round(n_local * 68 / ((ms_d + ms_f) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                if (ms_d + ms_f) > 0 else None,
+                # the same pass in the bytes the counters saw (lists, halo re-staging included): how busy HBM really is
+                "pass_traffic_frac_of_peak": round(pass_traffic_frac, 4) if pass_traffic_frac else None,
+            },
+            "kernels_ms": kernels_ms,
+            "slab_overlap": bool(world > 1 and drv.overlap),
+            "kernel_events": ("density / force kernels in the timed region, the others in a "
+                              f"{timed_launch_steps}-step segment after it") if events_in_region else
+                             f"separate {timed_launch_steps}-step segment after the timed region",
+            "max_vel": st.max_vel,
+            "max_cell_count": st.max_cell_count,
+            "developed": developed,
+            "drifted": drifted,
+            "exact": exact,
+            # DSL_OPT_SKIN: steps of the timed region that walked neighbour lists, and how many of them rebuilt the lists
+            # (sort + candidate sweep) -- the region holds the share of rebuilds this phase of the flow asks for
+            "skin": {"s": eng.get_option("skin"), "predict": opt_or("skin_predict"), "tau_steps_last_rebuild": round(skin_tau, 2),
+                     "steps_in_timed_region": int(skin1[0] - skin0[0]),
+                     "rebuilds_in_timed_region": int(skin1[1] - skin0[1]),
+                     "list_overflow": int(eng.get_option("skin_list_overflow")),
+                     # list fields per particle at the last rebuild: what the particles need, and what the walks visit
+                     # once every wave's lists are padded to its longest
+                     "fields_per_particle": round(skin_fields[0] / n_total, 2), "fields_walked_per_particle": round(skin_fields[1] / n_total, 2),
+                     "suspensions": int(eng.get_option("skin_suspensions"))} if world == 1 else None,
+            "n_live_rank0": n_live,
+            "slab_driver": (("native (dsl_slab_wcsph_step: RCCL inside libdslsph.so)" if backend == "nccl" else
+                             "native (dsl_slab_wcsph_step over a host-staged dsl_comm_create_custom transport)")
+                            if world > 1 and getattr(drv, "native", False)
+                            else ("python protocol" if world > 1 else None)),
+        }
 
     if rank == 0:
         value = n_total * args.steps / dt / 1e6
@@ -457,58 +545,14 @@ def main():
                 "parallelism": "single GPU" if world == 1 else f"{world} spatial slabs + 2h halo",
                 **({"library_options": args.opt} if args.opt else {}),
             },
-            "roofline": {
-                "bound": bound,
-                "kernel": kname,
-                "achieved": round(achieved, 2),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5),
-                "traffic": traffic,
-                "traffic_ratio": round(traffic / (n_local * kbytes), 3) if traffic else None,
-                "traffic_frac_of_peak": round(real_hbm_frac, 4) if real_hbm_frac else None,
-                "valu": valu,
-                "avg_ms": round(kms, 4),
-                "bytes_per_particle": kbytes,
-                "pass_density_ms": round(ms_d, 4),
-                "pass_force_ms": round(ms_f, 4),
-                "pass_frac_68B": round(n_local * 68 / ((ms_d + ms_f) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                if (ms_d + ms_f) > 0 else None,
-                # the same pass in the bytes the counters saw (lists, halo re-staging included): how busy HBM really is
-                "pass_traffic_frac_of_peak": round(pass_traffic_frac, 4) if pass_traffic_frac else None,
-            },
-            "kernels_ms": kernels_ms,
-            "slab_overflow": overflow,
-            "slab_band_missed": band_missed,
-            "slab_pci_query_escaped": query_escaped,
-            "slab_overlap": bool(world > 1 and drv.overlap),
-            "kernel_events": ("density / force kernels in the timed region, the others in a "
-                              f"{timed_launch_steps}-step segment after it") if events_in_region else
-                             f"separate {timed_launch_steps}-step segment after the timed region",
-            "max_vel": st.max_vel,
-            "max_cell_count": st.max_cell_count,
-            "developed": developed,
-            "drifted": drifted,
-            "exact": exact,
-            # DSL_OPT_SKIN: steps of the timed region that walked neighbour lists, and how many of them rebuilt the lists
-            # (sort + candidate sweep) -- the region holds the share of rebuilds this phase of the flow asks for
-            "skin": {"s": eng.get_option("skin"), "predict": opt_or("skin_predict"), "tau_steps_last_rebuild": round(skin_tau, 2),
-                     "steps_in_timed_region": int(skin1[0] - skin0[0]),
-                     "rebuilds_in_timed_region": int(skin1[1] - skin0[1]),
-                     "list_overflow": int(eng.get_option("skin_list_overflow")),
-                     # list fields per particle at the last rebuild: what the particles need, and what the walks visit
-                     # once every wave's lists are padded to its longest
-                     "fields_per_particle": round(skin_fields[0] / n_total, 2), "fields_walked_per_particle": round(skin_fields[1] / n_total, 2),
-                     "suspensions": int(eng.get_option("skin_suspensions"))} if world == 1 else None,
-            "n_live_rank0": n_live,
-            "n_ranks_seen_by_rccl": ranks_seen,
-            "slab_driver": (("native (dsl_slab_wcsph_step: RCCL inside libdslsph.so)" if backend == "nccl" else
-                             "native (dsl_slab_wcsph_step over a host-staged dsl_comm_create_custom transport)")
-                            if world > 1 and getattr(drv, "native", False)
-                            else ("python protocol" if world > 1 else None)),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args)
+        if world > 1 or args.full:  # (the status words that void a slab run)
+            out.update({"slab_overflow": overflow, "slab_band_missed": band_missed,
+                        "slab_pci_query_escaped": query_escaped, "n_ranks_seen_by_rccl": ranks_seen})
+        if args.full:
+            out.update(full)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     dog.disarm()
     if world > 1:

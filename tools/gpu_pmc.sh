@@ -1,11 +1,12 @@
 #!/bin/bash
 # rocprofv3 kernel stats + PMC passes of the bench command; summaries under gpurun_out/r2/ (copy into profiles/)
 set -o pipefail
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/r2
 mkdir -p $out
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+BENCH="python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 rocprofv3 -L > $out/counters_available.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- $BENCH > $out/prof_stats_bench.json 2> $out/prof_stats.err
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv 2>/dev/null
