@@ -471,6 +471,14 @@ int build_lsh(dsl_handle* h) {
   return DSL_OK;
 }
 
+// dsl_params.sort_unordered is honoured only where the in-cell order can cost no more than last bits: the
+// running-mass viscosity (sph_field.go:265, (force + t) * m) weights a neighbour's term by m^k, k its distance from
+// the end of the sum, so for m != 1 the order of the slots decides the force itself (WCSPH viscosity, ViscousAll
+// and PCISPH all sum it) and the cells stay ordered by particle id
+bool sort_ordered(const dsl_handle* h) {
+  return !h->prm.sort_unordered || (h->c.visc_running_mass && h->c.mass != 1.0f);
+}
+
 int build_grid(dsl_handle* h, bool carry_derived) {
   if (h->split_pending) return fail(h, DSL_ERR_INVALID, "a split force pass is in flight: finish it with DSL_SPLIT_INNER");
   if (h->lsh) return build_lsh(h);
@@ -480,7 +488,7 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   CSoa3 p = cpos(h);
   // (the histogram and the "cells to order" bitmap are clean: zeroed at creation, and again by
   // k_scan_apply / k_tile_list of the previous build)
-  const bool ordered = !h->prm.sort_unordered;
+  const bool ordered = sort_ordered(h);
   if (h->sort_scratch_dirty) {  // an earlier build stopped between k_cell_rank and the kernels that clean up behind it
     HIP_TRY(h, hipMemsetAsync(h->cell_count, 0, sizeof(int) * (size_t)h->ncell_pad, h->stream));
     if (h->unordered) HIP_TRY(h, hipMemsetAsync(h->unordered, 0, sizeof(unsigned int) * (size_t)(h->ncell_pad / 32), h->stream));
@@ -1730,7 +1738,7 @@ int skin_step(dsl_handle* h) {
   // sweep and the lists are built at, and what displacement is measured against
   const CSoa3 pR{h->pvr[0], h->pvr[1], h->pvr[2]};
   const Soa3 pRw{h->pvr[0], h->pvr[1], h->pvr[2]};
-  const bool ordered = !h->prm.sort_unordered;
+  const bool ordered = sort_ordered(h);
   hipLaunchKernelGGL(k_skin_decide, dim3(1), dim3(1), 0, h->stream, st);
   HIP_TRY(h, hipGetLastError());
   // the rebuild chain: launched every step, every kernel returns at once unless this step rebuilds

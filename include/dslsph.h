@@ -109,7 +109,10 @@ typedef struct dsl_params {
   /* 0 (default): slots inside a grid cell are ascending in particle id after every neighbour build, so
    * every neighbour sum runs in a fixed order and results are reproducible bit for bit from run to run
    * (and, in DSL_MATH_EXACT, equal to the reference's sums taken cell by cell).  1: keep the order the
-   * counting sort's atomics produce (saves the ordering pass of the scatter; last-bit differences between runs). */
+   * counting sort's atomics produce (saves the ordering pass of the scatter; last-bit differences between runs).
+   * Ignored -- the cells stay ordered -- while visc_running_mass = 1 and mass != 1: that viscosity (sph_field.go:265)
+   * multiplies its running sum by m after every neighbour, so the in-cell order would decide the viscous force of
+   * WCSPH, ViscousAll and PCISPH, not only its last bit. */
   int32_t sort_unordered;
   /* reserved[0]: budget, in MiB, for each of the two side arrays that cost memory per GRID CELL rather than per particle
    * (the cells' key rows of the one-pass in-cell ordering: 128 B per cell; the PCISPH query rows: 512 B per cell); 0 = the

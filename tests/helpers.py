@@ -44,13 +44,16 @@ def rel_err(a, b, floor=0.0):
     return float(np.max(np.abs(a - b)) / scale)
 
 
-def brute_force_step_f64(p, x, v, probe, near):
+def brute_force_step_f64(p, x, v, probe, near, force=None):
     """One WCSPH step of the build's fused force+integrate kernel, in float64, by brute force, for
     the particles `probe` (index array) of the state (x, v); `near` lists every particle within 2h of
     a probe particle.  The formulas are the reference's (std_kernel.go:33-76, model.go:92-101,
     sph_field.go:155-200,251-269 without the running-mass product, fluid.go:175-197) plus the
-    build-defined wall box.  Returns (rho_probe, x_new, v_new).  Independent of the oracle and of the
-    engine: numpy only."""
+    build-defined wall box.  `force`: the force each probe particle carries into the step, one row per
+    probe (an uploaded per-particle field); None: force_reset, the state after an Update.  The
+    running-mass viscosity (visc_running_mass = 1) is accepted for mass == 1, where its product
+    (force + t) * m is the plain sum.  Returns (rho_probe, x_new, v_new).  Independent of the oracle
+    and of the engine: numpy only."""
     h, m = float(p.h), float(p.mass)
     PI = 3.141592653589
     A, B, Ck = 315.0 / (64.0 * PI * h ** 3), -45.0 / (PI * h ** 4), 90.0 / (PI * h ** 5)
@@ -81,13 +84,16 @@ def brute_force_step_f64(p, x, v, probe, near):
         msk = (d2 < h * h) & (d2 > 0)
         r = np.sqrt(d2[msk])
         rho_p[k] = rho_n[i]
-        F = np.array([float(p.force_reset[a]) for a in range(3)])
+        if force is None:
+            F = np.array([float(p.force_reset[a]) for a in range(3)])
+        else:
+            F = np.asarray(force[k], dtype=np.float64).copy()
         if p.wcsph_pressure_force:
             grad = (d[msk] / r[:, None]) * (-(B * (1.0 - r / h) ** 2))[:, None]  # Grad = dir * (-O1D)
             G = ((pterm(rho_n[i]) + pterm(rho_n[msk]))[:, None] * grad).sum(axis=0)
             F = F + float(p.pressure_sign) * rho_n[i] * m * G
         if p.wcsph_viscosity:
-            assert not p.visc_running_mass
+            assert not p.visc_running_mass or float(p.mass) == 1.0, "the running-mass product is order-dependent for m != 1"
             V = (m * (vn[msk] - vn[i]) / rho_n[msk][:, None] * (Ck * (1.0 - r / h))[:, None]).sum(axis=0)
             F = F + float(p.mu) * V
         F = F + np.array([float(p.external[a]) for a in range(3)])
