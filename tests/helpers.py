@@ -127,3 +127,78 @@ def fast_velocity_tolerance(p, steps, eps_rho=2.0e-6):
     cells) measures up to 5e-6 (tools/pair_diag.py), and its tests pass 6e-6."""
     cs2 = float(p.eos_w) / float(p.mass)
     return 0.5 * float(p.eos_gamma) * eps_rho * cs2 / float(p.h) * float(p.dt) * steps
+
+
+SLAB_SENTINEL = np.uint32(0x7FC0DEAD)  # what a message buffer holds before a pack; a quiet-NaN pattern no record carries
+SLAB_RECORD_X = 4                      # position-only record: x, y, z, id bits
+
+
+def slab_message_reference(pos, vel, ids, axis, lo, hi, width_full, width, cap_full, cap_x, rec=7, pci_pos=None,
+                           pci_vel=None):
+    """What dsl_slab_pack has to leave in its two message buffers, word for word, written from include/dslsph.h and
+    the layout comments of kernels_grid.hpp (independent of oracle_slab_engine.py).
+
+    `pos`, `vel` (n x 3 float32) and `ids` (n int32) are the engine's state in SLOT order (download(...,
+    sorted_order=True), download_ids()); `pci_pos` / `pci_vel` the predictor state in the same order, needed for
+    rec = 13.  The slab owns [lo, hi) along `axis`.
+
+    Thresholds are sums of two floats, as the product computes them: full_lo = float32(lo) + float32(width_full),
+    band_lo = float32(lo) + float32(width), full_hi = float32(hi) - float32(width_full), band_hi = float32(hi) -
+    float32(width).  Lower message: p < full_lo is a full record, else p < band_lo a position-only record; upper
+    message: p >= full_hi full, else p >= band_hi position-only.  A NaN axis coordinate fails every comparison and
+    belongs to no band; an infinite plane (a domain end) leaves its message empty.  Records are in slot order.
+
+    Layout (32-bit words): a header of `rec` words, [0] / [1] the numbers of full / position-only records as int32
+    bits, clamped to the capacities; cap_full full records of `rec` words (x y z vx vy vz id [pci x y z, pci vx vy vz]);
+    cap_x position-only records of 4 words (x y z id).  Records that do not fit are dropped, the first ones in slot
+    order stay.
+
+    Returns {"lo": side, "hi": side}; a side is a dict with
+      counts   (nf, nx), UNclamped
+      words    uint32[(cap_full + 1) * rec + 4 * cap_x]: the message; words nobody writes hold SLAB_SENTINEL
+      written  bool mask of the same length: the words the pack writes -- every other word must keep what it held
+      full, xonly  slot indices of the records that were kept, in message order"""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 3)
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    assert rec in (7, 13) and pos.shape[0] == vel.shape[0] == ids.shape[0]
+    if rec == 13:
+        pci_pos = np.ascontiguousarray(pci_pos, np.float32).reshape(-1, 3)
+        pci_vel = np.ascontiguousarray(pci_vel, np.float32).reshape(-1, 3)
+    cap_full, cap_x = int(cap_full), int(cap_x)
+    f32 = np.float32
+    p = pos[:, axis]
+    with np.errstate(invalid="ignore", over="ignore"):
+        full_lo, band_lo = f32(lo) + f32(width_full), f32(lo) + f32(width)
+        full_hi, band_hi = f32(hi) - f32(width_full), f32(hi) - f32(width)
+        lo_full = p < full_lo
+        lo_x = ~lo_full & (p < band_lo)
+        hi_full = p >= full_hi
+        hi_x = ~hi_full & (p >= band_hi)
+    out = {}
+    for side, full, xonly in (("lo", lo_full, lo_x), ("hi", hi_full, hi_x)):
+        fi, xi = np.nonzero(full)[0], np.nonzero(xonly)[0]
+        nf, nx = int(fi.size), int(xi.size)
+        fi, xi = fi[:cap_full], xi[:cap_x]
+        words = np.full((cap_full + 1) * rec + cap_x * SLAB_RECORD_X, SLAB_SENTINEL, np.uint32)
+        written = np.zeros(words.shape, bool)
+        words[0:2] = np.array([min(nf, cap_full), min(nx, cap_x)], np.int32).view(np.uint32)
+        written[0:2] = True
+        r = words[rec:(cap_full + 1) * rec].reshape(cap_full, rec)
+        rw = written[rec:(cap_full + 1) * rec].reshape(cap_full, rec)
+        k = fi.size
+        r[:k, 0:3] = pos[fi].view(np.uint32)
+        r[:k, 3:6] = vel[fi].view(np.uint32)
+        r[:k, 6] = ids[fi].view(np.uint32)
+        if rec == 13:
+            r[:k, 7:10] = pci_pos[fi].view(np.uint32)
+            r[:k, 10:13] = pci_vel[fi].view(np.uint32)
+        rw[:k, :] = True
+        x = words[(cap_full + 1) * rec:].reshape(cap_x, SLAB_RECORD_X)
+        xw = written[(cap_full + 1) * rec:].reshape(cap_x, SLAB_RECORD_X)
+        k = xi.size
+        x[:k, 0:3] = pos[xi].view(np.uint32)
+        x[:k, 3] = ids[xi].view(np.uint32)
+        xw[:k, :] = True
+        out[side] = {"counts": (nf, nx), "words": words, "written": written, "full": fi, "xonly": xi}
+    return out

@@ -89,3 +89,49 @@ def test_slab_id_subsets_partition_the_block():
         assert np.array_equal(scenes.dambreak_positions_ids(n3, 0.1, a), full[a])
         lay = np.floor(full[a][:, axis] / 0.1).astype(int)
         assert lay.min() == 0 and lay.max() == 1
+
+
+def test_message_reference_matches_the_oracle_engine_word_for_word():
+    """helpers.slab_message_reference (the yardstick of tests/test_gpu_slab_messages.py, written from the header's
+    description of a message) against OracleSlabEngine.pack (written for the driver tests): the middle rank of a
+    3-slab split of the jittered 12^3 lattice, capacities that hold every record, both sides.  Every word either
+    of them writes must be the same word; the words behind the records are the oracle's zero fill on one side and
+    the reference's "never written" mask on the other."""
+    from dieselfluid_amd import scenes
+    from oracle_slab_engine import OracleSlabEngine
+    n3, axis = 12, 2
+    pos = helpers.jittered_lattice(n3)
+    vel = helpers.seeded_velocities(n3 ** 3)
+    gid = np.random.default_rng(5).permutation(n3 ** 3).astype(np.int32) + 1000
+    a = pos[:, axis]
+    step = (float(a.max()) - float(a.min())) / (n3 - 1)
+    planes = [float(a.min()) - 0.5 * step + r * 4 * step for r in range(4)]
+    lo, hi = planes[1], planes[2]
+    mine = (a >= np.float32(lo)) & (a < np.float32(hi))
+    width_full, width = 1.0 * step, 2.0 * step
+    p, _ = scenes.dambreak_scene(n3, math_mode=0, positions=False)
+    p.n_particles = int(mine.sum())
+    cap_full, cap_x = n3 * n3 * 2, n3 * n3 * 2
+    eng = OracleSlabEngine(p, 0, cap_full, cap_x)
+    eng.upload("positions", pos[mine])
+    eng.upload("velocities", vel[mine])
+    eng.set_ids(gid[mine])
+    eng.slab_config(axis, lo, hi)
+    got = eng.pack(width_full, width, True, True)
+    ref = helpers.slab_message_reference(pos[mine], vel[mine], gid[mine], axis, lo, hi, width_full, width, cap_full, cap_x)
+    for side, msg in zip(("lo", "hi"), got):
+        r = ref[side]
+        nf, nx = r["counts"]
+        # a layer of 144 particles per category, give or take the jitter; nothing is clamped
+        assert 100 < nf <= cap_full and 100 < nx <= cap_x
+        words = msg.numpy().view(np.uint32)
+        assert words.shape == r["words"].shape
+        w = r["written"]
+        assert np.array_equal(words[w], r["words"][w]), side
+        assert not words[~w].any(), "the oracle engine wrote a word the reference calls untouched"
+        assert np.all(r["words"][~w] == helpers.SLAB_SENTINEL)
+        assert eng.status()[2:] == (max(ref["lo"]["counts"][0], ref["hi"]["counts"][0]),
+                                    max(ref["lo"]["counts"][1], ref["hi"]["counts"][1]))
+    # the two messages of this slab share no particle (4 layers, bands of 2), and together they hold all of it
+    packed = np.concatenate([gid[mine][ref[s][k]] for s in ("lo", "hi") for k in ("full", "xonly")])
+    assert np.array_equal(np.sort(packed), np.sort(gid[mine]))
