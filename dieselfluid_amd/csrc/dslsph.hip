@@ -24,6 +24,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -424,6 +425,13 @@ Soa3 mfrc(dsl_handle* h) { return {h->frc[h->cur_f][0], h->frc[h->cur_f][1], h->
 CSoa3 cfrc(dsl_handle* h) { return {h->frc[h->cur_f][0], h->frc[h->cur_f][1], h->frc[h->cur_f][2]}; }
 Soa3 mpcip(dsl_handle* h) { return {h->pci[h->cur_pci][0], h->pci[h->cur_pci][1], h->pci[h->cur_pci][2]}; }
 Soa3 mpciv(dsl_handle* h) { return {h->pci[h->cur_pci][3], h->pci[h->cur_pci][4], h->pci[h->cur_pci][5]}; }
+Soa3 mxsph(dsl_handle* h) { return {h->xsph[0], h->xsph[1], h->xsph[2]}; }
+Soa3 mgterm(dsl_handle* h) { return {h->gterm[0], h->gterm[1], h->gterm[2]}; }
+constexpr Soa3 kNoSoa3{nullptr, nullptr, nullptr};
+CSoa3 as_const(Soa3 a) { return {a.x, a.y, a.z}; }
+// the PCISPH predictor state, or three nulls while PCISPH is not running
+Soa3 mpcip_if_active(dsl_handle* h) { return h->pci_active ? mpcip(h) : kNoSoa3; }
+Soa3 mpciv_if_active(dsl_handle* h) { return h->pci_active ? mpciv(h) : kNoSoa3; }
 
 inline int n_fluid_of(const dsl_handle* h) { return h->n - h->nb; }
 Bnd bnd_of(const dsl_handle* h) { return Bnd{h->nb > 0 ? h->ids[h->cur_ids] : nullptr, n_fluid_of(h)}; }
@@ -479,6 +487,40 @@ bool sort_ordered(const dsl_handle* h) {
   return !h->prm.sort_unordered || (h->c.visc_running_mass && h->c.mass != 1.0f);
 }
 
+// an earlier build stopped between k_cell_rank and the kernels that clean up behind it
+int clean_sort_scratch(dsl_handle* h) {
+  HIP_TRY(h, hipMemsetAsync(h->cell_count, 0, sizeof(int) * (size_t)h->ncell_pad, h->stream));
+  if (h->unordered) HIP_TRY(h, hipMemsetAsync(h->unordered, 0, sizeof(unsigned int) * (size_t)(h->ncell_pad / 32), h->stream));
+  return DSL_OK;
+}
+
+// exclusive prefix of a per-cell histogram (the particles', the PCISPH queries'): `count` -> `start`; leaves `count` zeroed
+void launch_scan(dsl_handle* h, int* count, int* sums, int* start, DevStats* stats, int* n_tiles, SkinGate gate = SkinGate{nullptr}) {
+  hipLaunchKernelGGL(k_scan_sums, dim3(h->nscan), dim3(kBlock), 0, h->stream, count, sums, stats, n_tiles, gate);
+  hipLaunchKernelGGL(k_scan_apply, dim3(h->nscan), dim3(kBlock), 0, h->stream, count, sums, start, stats, gate);
+}
+
+inline int tile_desc_grid(const dsl_handle* h) { return std::min(h->tg.ntiles, 8192); }
+
+// the lists of non-empty tiles and their tables, once per build for every kernel that sweeps tiles
+void launch_tile_tables(dsl_handle* h, int* n_live, SkinGate gate = SkinGate{nullptr}) {
+  hipLaunchKernelGGL(k_tile_list, dim3(grid_for(h->tg.nlist)), dim3(kBlock), 0, h->stream, h->c, h->tg, h->cell_start, h->tiles,
+                     h->n_tiles, h->n_tiles + 5, n_live, h->tile_desc_of, h->unordered, h->ncell_pad / 32, h->dcounter + 3, gate);
+  hipLaunchKernelGGL(k_tile_desc, dim3(tile_desc_grid(h)), dim3(kWave), 0, h->stream, h->c, h->tg, h->cell_start, h->cell_start,
+                     h->tiles, h->n_tiles, h->tile_desc, nullptr, kTCap, gate);
+}
+
+// PCISPH with binned queries: the tiles that hold queries, and their tables.  rows: the cells' query counts stand in for
+// the queries' prefix (kernels_tiled.hpp: tile_setup_load_counts), and keep_counts leaves them standing
+void launch_query_tile_tables(dsl_handle* h, bool rows, bool keep_counts) {
+  const dim3 g(grid_for(h->tg.nlist)), b(kBlock);
+  if (rows) hipLaunchKernelGGL(k_qtile_list<true>, g, b, 0, h->stream, h->c, h->tg, h->qcount, h->qtiles, h->n_qtiles, h->dstats);
+  else hipLaunchKernelGGL(k_qtile_list<false>, g, b, 0, h->stream, h->c, h->tg, h->qstart, h->qtiles, h->n_qtiles, h->dstats);
+  hipLaunchKernelGGL(k_tile_desc, dim3(tile_desc_grid(h)), dim3(kWave), 0, h->stream, h->c, h->tg, h->cell_start,
+                     rows ? nullptr : h->qstart, h->qtiles, h->n_qtiles, h->qtile_desc, rows ? h->qcount : nullptr, kTCap,
+                     SkinGate{nullptr}, keep_counts);
+}
+
 int build_grid(dsl_handle* h, bool carry_derived) {
   if (h->split_pending) return fail(h, DSL_ERR_INVALID, "a split force pass is in flight: finish it with DSL_SPLIT_INNER");
   if (h->lsh) return build_lsh(h);
@@ -489,10 +531,8 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   // (the histogram and the "cells to order" bitmap are clean: zeroed at creation, and again by
   // k_scan_apply / k_tile_list of the previous build)
   const bool ordered = sort_ordered(h);
-  if (h->sort_scratch_dirty) {  // an earlier build stopped between k_cell_rank and the kernels that clean up behind it
-    HIP_TRY(h, hipMemsetAsync(h->cell_count, 0, sizeof(int) * (size_t)h->ncell_pad, h->stream));
-    if (h->unordered) HIP_TRY(h, hipMemsetAsync(h->unordered, 0, sizeof(unsigned int) * (size_t)(h->ncell_pad / 32), h->stream));
-  }
+  if (h->sort_scratch_dirty)
+    if (int rc = clean_sort_scratch(h)) return rc;
   h->sort_scratch_dirty = true;
   // PCISPH: "a particle lies outside the grid's bounds" (dcounter[4] = the number of the last build that saw one;
   // k_pci_predict_bin finishes far-away queries on the spot when this build saw none)
@@ -509,10 +549,7 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   });
   if (rc) return rc;
   rc = timed(h, DSL_K_SCAN, [&] {
-    hipLaunchKernelGGL(k_scan_sums, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->cell_count, h->block_sums, h->dstats,
-                       !h->lsh ? h->n_tiles : nullptr);
-    hipLaunchKernelGGL(k_scan_apply, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->cell_count, h->block_sums,
-                       h->cell_start, h->dstats);
+    launch_scan(h, h->cell_count, h->block_sums, h->cell_start, h->dstats, !h->lsh ? h->n_tiles : nullptr);
   });
   if (rc) return rc;
   ScatterArrays a{};
@@ -569,14 +606,7 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   if (h->pci_active) h->cur_pci ^= 1;
   h->grid_valid = true;
   if (!h->lsh) {
-    rc = timed(h, DSL_K_TILE_LIST, [&] {
-      hipLaunchKernelGGL(k_tile_list, dim3(grid_for(h->tg.nlist)), dim3(kBlock), 0, h->stream, h->c, h->tg,
-                         h->cell_start, h->tiles, h->n_tiles, h->n_tiles + 5, h->c.n_ptr ? h->dn : nullptr, h->tile_desc_of,
-                         h->unordered, h->ncell_pad / 32, h->dcounter + 3);
-      // the tables of the non-empty tiles, once per build for every kernel that sweeps tiles
-      hipLaunchKernelGGL(k_tile_desc, dim3(std::min(h->tg.ntiles, 8192)), dim3(kWave), 0, h->stream, h->c, h->tg,
-                         h->cell_start, h->cell_start, h->tiles, h->n_tiles, h->tile_desc);
-    });
+    rc = timed(h, DSL_K_TILE_LIST, [&] { launch_tile_tables(h, h->c.n_ptr ? h->dn : nullptr); });
     if (rc) return rc;
     h->sort_scratch_dirty = false;  // k_scan_apply and k_tile_list are queued: they leave both arrays clean
   }
@@ -590,11 +620,16 @@ int build_grid(dsl_handle* h, bool carry_derived) {
 
 int ensure_grid(dsl_handle* h) { return h->grid_valid ? DSL_OK : build_grid(h, true); }
 
-template <class Launch>
-int by_math(dsl_handle* h, Launch&& l) {
-  if (h->prm.math_mode == DSL_MATH_FAST) l(std::true_type{});
-  else l(std::false_type{});
-  return DSL_OK;
+// A runtime switch becomes a template argument: `f` is a generic lambda and reads its flag as decltype(flag)::value.
+// Nested calls give several flags; which combinations get a kernel is written as `if constexpr` at the launch.
+template <class F>
+void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class F>
+void by_math(dsl_handle* h, F&& f) {
+  with_flag(h->prm.math_mode == DSL_MATH_FAST, f);
 }
 
 // FAST mode uses the LDS-tiled kernels; the reference's running-mass viscosity recurrence
@@ -663,21 +698,18 @@ int density_pass(dsl_handle* h) {
     // both instantiations are launched; the one the tile statistics of this build do not ask for
     // returns at once (kernels_tiled.hpp: share_wanted)
     int rc = timed(h, DSL_K_DENSITY, [&] {
-#define DSL_LAUNCH_DENSITY(KERNEL)                                                                                   \
-  hipLaunchKernelGGL(KERNEL, dim3(persistent_grid(h, 4)), dim3(kTBlock), 0, h->stream, c, h->tg, h->tile_desc_of, h->n_tiles, \
-                     h->tile_desc, h->cell_start, bnd_of(h), p, h->rho, h->pterm, h->nmask, h->cap)
-      if (h->density_pair) {  // two targets per lane (kernels_tiled.hpp: k_density_pair), 256-thread workgroups, four per CU
-#define DSL_LAUNCH_PAIR(KERNEL)                                                                                      \
-  hipLaunchKernelGGL(KERNEL, dim3(persistent_grid(h, 8)), dim3(kPBlock), 0, h->stream, c, h->tg, h->tile_desc_of, h->n_tiles, \
-                     h->tile_desc, h->cell_start, bnd_of(h), p, h->rho, h->pterm, h->nmask, h->cap)
-        if (c.slab_axis < 0) DSL_LAUNCH_PAIR(k_density_pair<false>);
-        DSL_LAUNCH_PAIR(k_density_pair<true>);
-#undef DSL_LAUNCH_PAIR
-        return;
-      }
-      if (c.slab_axis < 0) DSL_LAUNCH_DENSITY(k_density_tiled<false>);
-      DSL_LAUNCH_DENSITY(k_density_tiled<true>);
-#undef DSL_LAUNCH_DENSITY
+      auto launch = [&](auto share) {
+        constexpr bool SHARE = decltype(share)::value;
+        if (h->density_pair)  // two targets per lane (kernels_tiled.hpp: k_density_pair), 256-thread workgroups, four per CU
+          hipLaunchKernelGGL(k_density_pair<SHARE>, dim3(persistent_grid(h, 8)), dim3(kPBlock), 0, h->stream, c, h->tg,
+                             h->tile_desc_of, h->n_tiles, h->tile_desc, h->cell_start, bnd_of(h), p, h->rho, h->pterm, h->nmask, h->cap);
+        else
+          hipLaunchKernelGGL(k_density_tiled<SHARE>, dim3(persistent_grid(h, 4)), dim3(kTBlock), 0, h->stream, c, h->tg,
+                             h->tile_desc_of, h->n_tiles, h->tile_desc, h->cell_start, bnd_of(h), p, h->rho, h->pterm, h->nmask, h->cap);
+      };
+      // (a slab always has half-empty ghost tiles: its ranks run the pass-sharing instantiation only)
+      if (c.slab_axis < 0) launch(std::false_type{});
+      launch(std::true_type{});
     });
     if (rc) return rc;
     h->dens_fresh = h->dens_held = true;
@@ -736,80 +768,44 @@ int force_integrate(dsl_handle* h, int part = 0) {
       // of the CUs (+6 % on its own time).
       if (part == 2 && gsz >= 64) gsz = (gsz - gsz / 8) & ~7;
       dim3 g(gsz), b(kTBlock);
-#define DSL_LAUNCH_FT4(GG, VV, XX, SS, HH)                                                                       \
-  if (!(SS) && wq != nullptr) DSL_LAUNCH_FT5(GG, VV, XX, false, HH, true);                                       \
-  else DSL_LAUNCH_FT5(GG, VV, XX, SS, HH, false)
-#define DSL_LAUNCH_FT5(GG, VV, XX, SS, HH, QQ)                                                                   \
-  hipLaunchKernelGGL((k_force_integrate_tiled<GG, VV, kOutIntegrate, XX, SS, HH, false, QQ>), g, b, 0, h->stream, c, \
-                     h->tg, tiles, n_tiles, gtiles, n_gtiles, h->tile_desc, h->cell_start, p, v, h->rho, h->pterm, f, uni,   \
-                     po, vo, h->dstats, h->masks_valid ? h->nmask : nullptr, h->cap, ((XX) || (SS)) ? nullptr : h->n_tiles, bnd_of(h), \
-                     Soa3{nullptr, nullptr, nullptr}, wq)
-  // (the XSPH / cohesion variant and the slab variant -- a slab always has half-empty ghost tiles -- exist
-  // as the pass-sharing instantiation only; of the other two the device picks: kernels_tiled.hpp, share_wanted)
-#define DSL_LAUNCH_FT3(GG, VV, XX, SS)                                        \
-  do {                                                                        \
-    if ((XX) || (SS)) DSL_LAUNCH_FT4(GG, VV, XX, SS, true);                   \
-    else {                                                                    \
-      DSL_LAUNCH_FT4(GG, VV, false, SS, false);                               \
-      DSL_LAUNCH_FT4(GG, VV, false, SS, true);                                \
-    }                                                                         \
-  } while (0)
-#define DSL_LAUNCH_FT2(GG, VV, XX)                     \
-  do {                                                \
-    if (c.slab_axis >= 0) DSL_LAUNCH_FT3(GG, VV, XX, true); \
-    else DSL_LAUNCH_FT3(GG, VV, XX, false);           \
-  } while (0)
-#define DSL_LAUNCH_FT(GG, VV)                 \
-  do {                                        \
-    if (XS) DSL_LAUNCH_FT2(GG, VV, true);     \
-    else DSL_LAUNCH_FT2(GG, VV, false);       \
-  } while (0)
       const bool XS = c.xsph_eps != 0.0f || c.st_kappa != 0.0f;
-      if (G && V) DSL_LAUNCH_FT(true, true);
-      else if (G) DSL_LAUNCH_FT(true, false);
-      else if (V) DSL_LAUNCH_FT(false, true);
-      else DSL_LAUNCH_FT(false, false);
-#undef DSL_LAUNCH_FT5
-#undef DSL_LAUNCH_FT4
-#undef DSL_LAUNCH_FT3
-#undef DSL_LAUNCH_FT2
-#undef DSL_LAUNCH_FT
+      with_flag(G, [&](auto fg) { with_flag(V, [&](auto fv) { with_flag(XS, [&](auto fx) { with_flag(slab, [&](auto fs) {
+        with_flag(wq != nullptr, [&](auto fq) {
+          constexpr bool GG = decltype(fg)::value, VV = decltype(fv)::value, XX = decltype(fx)::value, SS = decltype(fs)::value;
+          // the tile queue has no slab instantiation: the band and interior launches of a slab rank overlap on two
+          // streams and walk lists other than list 0 (walk_ctr_of hands a slab rank no counters)
+          constexpr bool QQ = decltype(fq)::value && !SS;
+          auto launch = [&](auto share) {
+            hipLaunchKernelGGL((k_force_integrate_tiled<GG, VV, kOutIntegrate, XX, SS, decltype(share)::value, false, QQ>), g, b, 0,
+                               h->stream, c, h->tg, tiles, n_tiles, gtiles, n_gtiles, h->tile_desc, h->cell_start, p, v, h->rho,
+                               h->pterm, f, uni, po, vo, h->dstats, h->masks_valid ? h->nmask : nullptr, h->cap,
+                               (XX || SS) ? nullptr : h->n_tiles, bnd_of(h), kNoSoa3, wq);
+          };
+          // the XSPH / cohesion variant and the slab variant -- a slab always has half-empty ghost tiles -- exist as the
+          // pass-sharing instantiation only; of the other two the device picks (kernels_tiled.hpp: share_wanted)
+          if constexpr (!(XX || SS)) launch(std::false_type{});
+          launch(std::true_type{});
+        });
+      }); }); }); });
     });
   } else if (exact_tiled(h) && h->masks_valid) {
     rc = timed(h, DSL_K_FORCE_INTEGRATE, [&] {
       dim3 g(persistent_grid(h, 2)), b(kTBlock);
       const bool XS = c.xsph_eps != 0.0f || c.st_kappa != 0.0f;
-#define DSL_LAUNCH_FX(GG, VV, XX)                                                                                  \
-  hipLaunchKernelGGL((k_force_integrate_tiled<GG, VV, kOutIntegrate, XX, false, false, true>), g, b, 0, h->stream, c, \
-                     h->tg, tiles, n_tiles, gtiles, n_gtiles, h->tile_desc, h->cell_start, p, v, h->rho, h->pterm, f, uni, po, vo, \
-                     h->dstats, h->nmask, h->cap, nullptr, bnd_of(h), Soa3{nullptr, nullptr, nullptr})
-      if (XS) {
-        if (G && V) DSL_LAUNCH_FX(true, true, true);
-        else if (G) DSL_LAUNCH_FX(true, false, true);
-        else if (V) DSL_LAUNCH_FX(false, true, true);
-        else DSL_LAUNCH_FX(false, false, true);
-      } else {
-        if (G && V) DSL_LAUNCH_FX(true, true, false);
-        else if (G) DSL_LAUNCH_FX(true, false, false);
-        else if (V) DSL_LAUNCH_FX(false, true, false);
-        else DSL_LAUNCH_FX(false, false, false);
-      }
-#undef DSL_LAUNCH_FX
+      with_flag(G, [&](auto fg) { with_flag(V, [&](auto fv) { with_flag(XS, [&](auto fx) {
+        hipLaunchKernelGGL((k_force_integrate_tiled<decltype(fg)::value, decltype(fv)::value, kOutIntegrate, decltype(fx)::value,
+                                                    false, false, true>),
+                           g, b, 0, h->stream, c, h->tg, tiles, n_tiles, gtiles, n_gtiles, h->tile_desc, h->cell_start, p, v,
+                           h->rho, h->pterm, f, uni, po, vo, h->dstats, h->nmask, h->cap, nullptr, bnd_of(h), kNoSoa3);
+      }); }); });
     });
   } else
   rc = timed(h, DSL_K_FORCE_INTEGRATE, [&] {
-    by_math(h, [&](auto fast) {
-      constexpr bool FAST = decltype(fast)::value;
-      dim3 g(grid_for(launch_n(h))), b(kBlock);
-#define DSL_LAUNCH_FI(GG, VV)                                                                                    \
-  hipLaunchKernelGGL((k_force_integrate<FAST, GG, VV>), g, b, 0, h->stream, c, neigh(h), bnd_of(h), p, v, h->rho,          \
-                     h->pterm, f, uni, po, vo, h->dstats)
-      if (G && V) DSL_LAUNCH_FI(true, true);
-      else if (G) DSL_LAUNCH_FI(true, false);
-      else if (V) DSL_LAUNCH_FI(false, true);
-      else DSL_LAUNCH_FI(false, false);
-#undef DSL_LAUNCH_FI
-    });
+    dim3 g(grid_for(launch_n(h))), b(kBlock);
+    by_math(h, [&](auto fast) { with_flag(G, [&](auto fg) { with_flag(V, [&](auto fv) {
+      hipLaunchKernelGGL((k_force_integrate<decltype(fast)::value, decltype(fg)::value, decltype(fv)::value>), g, b, 0, h->stream,
+                         c, neigh(h), bnd_of(h), p, v, h->rho, h->pterm, f, uni, po, vo, h->dstats);
+    }); }); });
   });
   if (rc) return rc;
   if (part == 1) return DSL_OK;
@@ -839,7 +835,7 @@ int viscous_pass(dsl_handle* h, int with_xs = 0) {
   const DevConsts& c = h->c;
   CSoa3 p = cpos(h), v = cvel(h);
   Soa3 f = mfrc(h);
-  Soa3 xs{h->xsph[0], h->xsph[1], h->xsph[2]};
+  Soa3 xs = mxsph(h);
   return timed(h, DSL_K_VISCOUS, [&] {
     by_math(h, [&](auto fast) {
       hipLaunchKernelGGL((k_viscous<decltype(fast)::value>), dim3(grid_for(launch_n(h))), dim3(kBlock), 0, h->stream, c,
@@ -851,7 +847,7 @@ int viscous_pass(dsl_handle* h, int with_xs = 0) {
 // use_xs: Update advects positions with v + the XSPH correction stored by the viscous sweep
 int update_pass(dsl_handle* h, bool use_xs = false) {
   const DevConsts& c = h->c;
-  CSoa3 xs{use_xs ? h->xsph[0] : nullptr, use_xs ? h->xsph[1] : nullptr, use_xs ? h->xsph[2] : nullptr};
+  CSoa3 xs = as_const(use_xs ? mxsph(h) : kNoSoa3);
   Soa3 p = mpos(h, h->cur_pv), v = mvel(h, h->cur_pv);
   CSoa3 f = cfrc(h);
   const int uni = h->forces_uniform ? 1 : 0;
@@ -879,24 +875,24 @@ int host_count(dsl_handle* h, int* out) {
   return DSL_OK;
 }
 
-struct BufInfo {
+// The device arrays behind a host buffer id, in slot order: a[0 .. comps-1]; comps = 0: no such buffer.  The ids and
+// component counts are always valid; the callers see to it that the arrays hold what the id names (forces and pressures
+// materialised, the PCISPH state allocated and started) before they use the pointers.
+struct BufArrays {
   int comps;
+  float* a[3];
 };
-bool buf_info(int buffer, BufInfo& bi) {
+BufArrays buf_arrays(dsl_handle* h, int buffer) {
+  auto three = [](Soa3 s) { return BufArrays{3, {s.x, s.y, s.z}}; };
   switch (buffer) {
-    case DSL_BUF_POSITIONS:
-    case DSL_BUF_VELOCITIES:
-    case DSL_BUF_FORCES:
-    case DSL_BUF_PCI_POSITIONS:
-    case DSL_BUF_PCI_VELOCITIES:
-      bi.comps = 3;
-      return true;
-    case DSL_BUF_DENSITIES:
-    case DSL_BUF_PRESSURES:
-      bi.comps = 1;
-      return true;
-    default:
-      return false;
+    case DSL_BUF_POSITIONS: return three(mpos(h, h->cur_pv));
+    case DSL_BUF_VELOCITIES: return three(mvel(h, h->cur_pv));
+    case DSL_BUF_FORCES: return three(mfrc(h));
+    case DSL_BUF_PCI_POSITIONS: return three(mpcip(h));
+    case DSL_BUF_PCI_VELOCITIES: return three(mpciv(h));
+    case DSL_BUF_DENSITIES: return BufArrays{1, {h->rho, nullptr, nullptr}};
+    case DSL_BUF_PRESSURES: return BufArrays{1, {h->press, nullptr, nullptr}};
+    default: return BufArrays{0, {nullptr, nullptr, nullptr}};
   }
 }
 
@@ -1275,15 +1271,15 @@ int dsl_use_own_stream(dsl_handle* h) {
 
 int dsl_upload(dsl_handle* h, int buffer, const float* host, size_t count) {
   CHECK_HANDLE(h);
-  BufInfo bi;
-  if (!host || !buf_info(buffer, bi)) return fail(h, DSL_ERR_INVALID, "dsl_upload: bad buffer id or null pointer");
+  const int comps = buf_arrays(h, buffer).comps;
+  if (!host || !comps) return fail(h, DSL_ERR_INVALID, "dsl_upload: bad buffer id or null pointer");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   // positions hold Total() particles, everything else N() (particle_array.go:18-33)
   const bool with_boundary = h->nb > 0;
   const int limit = (buffer == DSL_BUF_POSITIONS || !with_boundary) ? ncur : n_fluid_of(h);
   const size_t n = (size_t)ncur;
-  if (count != (size_t)limit * bi.comps)
+  if (count != (size_t)limit * comps)
     return fail(h, DSL_ERR_INVALID,
                 with_boundary ? "dsl_upload: count does not match the buffer size (positions: N + Nboundary particles, others: N)"
                               : "dsl_upload: count does not match the buffer size");
@@ -1291,53 +1287,39 @@ int dsl_upload(dsl_handle* h, int buffer, const float* host, size_t count) {
   HIP_TRY(h, hipMemcpyAsync(h->stage, host, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
   const int* ids = h->ids[h->cur_ids];
   dim3 g(grid_for(h->n)), b(kBlock);
+  if (buffer == DSL_BUF_PCI_POSITIONS || buffer == DSL_BUF_PCI_VELOCITIES) {
+    if (int rc = alloc_pci(h)) return rc;
+    if (!h->pci_active) {
+      // pcisph_darwin.go:28-41: the state starts as a copy of positions/velocities
+      for (int k = 0; k < 6; ++k)
+        HIP_TRY(h, hipMemcpyAsync(h->pci[h->cur_pci][k], h->pv[h->cur_pv][k], n * sizeof(float),
+                                  hipMemcpyDeviceToDevice, h->stream));
+      h->pci_active = true;
+    }
+  }
+  const BufArrays d = buf_arrays(h, buffer);
+  if (comps == 3) {
+    const bool b0 = buffer == DSL_BUF_POSITIONS && with_boundary;  // Get(N()) is the zero particle (particle_array.go:98,107)
+    if (b0) std::memcpy(h->b0_pos, host + (size_t)3 * n_fluid_of(h), sizeof(h->b0_pos));
+    hipLaunchKernelGGL(k_unpack3, g, b, 0, h->stream, h->n, h->stage, ids, d.a[0], d.a[1], d.a[2], limit, b0 ? n_fluid_of(h) : -1);
+  } else {
+    hipLaunchKernelGGL(k_unpack1, g, b, 0, h->stream, h->n, h->stage, ids, d.a[0], limit);
+  }
   switch (buffer) {
-    case DSL_BUF_POSITIONS: {
-      Soa3 p = mpos(h, h->cur_pv);
-      const int zero_id = with_boundary ? n_fluid_of(h) : -1;  // Get(N()) is the zero particle (particle_array.go:98,107)
-      if (with_boundary) std::memcpy(h->b0_pos, host + (size_t)3 * n_fluid_of(h), sizeof(h->b0_pos));
-      hipLaunchKernelGGL(k_unpack3, g, b, 0, h->stream, h->n, h->stage, ids, p.x, p.y, p.z, limit, zero_id);
+    case DSL_BUF_POSITIONS:
       h->grid_valid = false;
       h->masks_valid = false;
       break;
-    }
-    case DSL_BUF_VELOCITIES: {
-      Soa3 v = mvel(h, h->cur_pv);
-      hipLaunchKernelGGL(k_unpack3, g, b, 0, h->stream, h->n, h->stage, ids, v.x, v.y, v.z, limit, -1);
-      break;
-    }
-    case DSL_BUF_FORCES: {
-      Soa3 f = mfrc(h);
-      hipLaunchKernelGGL(k_unpack3, g, b, 0, h->stream, h->n, h->stage, ids, f.x, f.y, f.z, limit, -1);
-      h->forces_uniform = false;
-      break;
-    }
+    case DSL_BUF_FORCES: h->forces_uniform = false; break;
     case DSL_BUF_DENSITIES:
-      hipLaunchKernelGGL(k_unpack1, g, b, 0, h->stream, h->n, h->stage, ids, h->rho, limit);
       // pterm must follow an uploaded density
       by_math(h, [&](auto fast) {
         hipLaunchKernelGGL((k_pterm<decltype(fast)::value>), g, b, 0, h->stream, h->c, bnd_of(h), h->rho, h->pterm);
       });
       h->dens_fresh = h->dens_held = true;
       break;
-    case DSL_BUF_PRESSURES:
-      hipLaunchKernelGGL(k_unpack1, g, b, 0, h->stream, h->n, h->stage, ids, h->press, limit);
-      h->press_zero = false;
-      break;
-    case DSL_BUF_PCI_POSITIONS:
-    case DSL_BUF_PCI_VELOCITIES: {
-      if (int rc = alloc_pci(h)) return rc;
-      if (!h->pci_active) {
-        // pcisph_darwin.go:28-41: the state starts as a copy of positions/velocities
-        for (int k = 0; k < 6; ++k)
-          HIP_TRY(h, hipMemcpyAsync(h->pci[h->cur_pci][k], h->pv[h->cur_pv][k], n * sizeof(float),
-                                    hipMemcpyDeviceToDevice, h->stream));
-        h->pci_active = true;
-      }
-      Soa3 d = buffer == DSL_BUF_PCI_POSITIONS ? mpcip(h) : mpciv(h);
-      hipLaunchKernelGGL(k_unpack3, g, b, 0, h->stream, h->n, h->stage, ids, d.x, d.y, d.z, limit, -1);
-      break;
-    }
+    case DSL_BUF_PRESSURES: h->press_zero = false; break;
+    default: break;
   }
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // host pointer is not retained (cgo rule)
@@ -1358,11 +1340,7 @@ int dsl_add_boundary_particles(dsl_handle* h, const float* host_positions, size_
   const int n_fluid = n_fluid_of(h);
   if (first) std::memcpy(h->b0_pos, host_positions, sizeof(h->b0_pos));
   Soa3 p = mpos(h, h->cur_pv), v = mvel(h, h->cur_pv);
-  Soa3 pcip{nullptr, nullptr, nullptr}, pciv{nullptr, nullptr, nullptr};
-  if (h->pci_active) {
-    pcip = mpcip(h);
-    pciv = mpciv(h);
-  }
+  Soa3 pcip = mpcip_if_active(h), pciv = mpciv_if_active(h);
   hipLaunchKernelGGL(k_append_boundary, dim3(grid_for(nb)), dim3(kBlock), 0, h->stream, nb, h->n, h->n, n_fluid, h->stage,
                      p.x, p.y, p.z, v.x, v.y, v.z, h->ids[h->cur_ids], pcip, pciv, h->rho, h->pterm);
   HIP_TRY(h, hipGetLastError());
@@ -1381,15 +1359,15 @@ int dsl_add_boundary_particles(dsl_handle* h, const float* host_positions, size_
 
 static int download_impl(dsl_handle* h, int buffer, float* host, size_t count, int sorted_order) {
   CHECK_HANDLE(h);
-  BufInfo bi;
-  if (!host || !buf_info(buffer, bi)) return fail(h, DSL_ERR_INVALID, "dsl_download: bad buffer id or null pointer");
+  const int comps = buf_arrays(h, buffer).comps;
+  if (!host || !comps) return fail(h, DSL_ERR_INVALID, "dsl_download: bad buffer id or null pointer");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   const bool with_boundary = h->nb > 0;
   const int limit = (buffer == DSL_BUF_POSITIONS || !with_boundary) ? ncur : n_fluid_of(h);
   if (with_boundary && sorted_order && buffer != DSL_BUF_POSITIONS)
     return fail(h, DSL_ERR_UNSUPPORTED, "dsl_download_sorted: with boundary particles only positions have a slot-order image");
-  if (count != (size_t)limit * bi.comps)
+  if (count != (size_t)limit * comps)
     return fail(h, DSL_ERR_INVALID,
                 with_boundary ? "dsl_download: count does not match the buffer size (positions: N + Nboundary particles, others: N)"
                               : "dsl_download: count does not match the buffer size");
@@ -1397,38 +1375,15 @@ static int download_impl(dsl_handle* h, int buffer, float* host, size_t count, i
     return fail(h, DSL_ERR_INVALID, "dsl_download: host order is gone after dsl_set_ids; use dsl_download_sorted + dsl_download_ids");
   const int* ids = h->ids[h->cur_ids];
   dim3 g(grid_for(h->n)), b(kBlock);
-  switch (buffer) {
-    case DSL_BUF_POSITIONS: {
-      CSoa3 p = cpos(h);
-      hipLaunchKernelGGL(k_pack3, g, b, 0, h->stream, h->n, h->stage, ids, p.x, p.y, p.z, sorted_order);
-      break;
-    }
-    case DSL_BUF_VELOCITIES: {
-      CSoa3 v = cvel(h);
-      hipLaunchKernelGGL(k_pack3, g, b, 0, h->stream, h->n, h->stage, ids, v.x, v.y, v.z, sorted_order);
-      break;
-    }
-    case DSL_BUF_FORCES: {
-      if (int rc = materialise_forces(h)) return rc;
-      CSoa3 f = cfrc(h);
-      hipLaunchKernelGGL(k_pack3, g, b, 0, h->stream, h->n, h->stage, ids, f.x, f.y, f.z, sorted_order);
-      break;
-    }
-    case DSL_BUF_DENSITIES:
-      hipLaunchKernelGGL(k_pack1, g, b, 0, h->stream, h->n, h->stage, ids, h->rho, sorted_order);
-      break;
-    case DSL_BUF_PRESSURES:
-      if (int rc = materialise_press(h)) return rc;
-      hipLaunchKernelGGL(k_pack1, g, b, 0, h->stream, h->n, h->stage, ids, h->press, sorted_order);
-      break;
-    case DSL_BUF_PCI_POSITIONS:
-    case DSL_BUF_PCI_VELOCITIES: {
-      if (!h->pci_active) return fail(h, DSL_ERR_INVALID, "dsl_download: PCISPH state not initialised (dsl_pcisph_begin)");
-      Soa3 s = buffer == DSL_BUF_PCI_POSITIONS ? mpcip(h) : mpciv(h);
-      hipLaunchKernelGGL(k_pack3, g, b, 0, h->stream, h->n, h->stage, ids, s.x, s.y, s.z, sorted_order);
-      break;
-    }
-  }
+  if (buffer == DSL_BUF_FORCES)
+    if (int rc = materialise_forces(h)) return rc;
+  if (buffer == DSL_BUF_PRESSURES)
+    if (int rc = materialise_press(h)) return rc;
+  if ((buffer == DSL_BUF_PCI_POSITIONS || buffer == DSL_BUF_PCI_VELOCITIES) && !h->pci_active)
+    return fail(h, DSL_ERR_INVALID, "dsl_download: PCISPH state not initialised (dsl_pcisph_begin)");
+  const BufArrays s = buf_arrays(h, buffer);
+  if (comps == 3) hipLaunchKernelGGL(k_pack3, g, b, 0, h->stream, h->n, h->stage, ids, s.a[0], s.a[1], s.a[2], sorted_order);
+  else hipLaunchKernelGGL(k_pack1, g, b, 0, h->stream, h->n, h->stage, ids, s.a[0], sorted_order);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(host, h->stage, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1470,9 +1425,9 @@ int dsl_download_decimated(dsl_handle* h, int buffer, int stride, float* host, s
     return fail(h, DSL_ERR_INVALID, "dsl_download_decimated: positions or velocities, stride >= 1");
   const size_t want = 3 * (((size_t)n + stride - 1) / stride);
   if (count != want) return fail(h, DSL_ERR_INVALID, "dsl_download_decimated: count must be 3*ceil(N/stride)");
-  CSoa3 a = buffer == DSL_BUF_POSITIONS ? cpos(h) : cvel(h);
+  const BufArrays a = buf_arrays(h, buffer);
   hipLaunchKernelGGL(k_pack3_decimated, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, n, stride, h->stage,
-                     h->ids[h->cur_ids], a.x, a.y, a.z);
+                     h->ids[h->cur_ids], a.a[0], a.a[1], a.a[2]);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(host, h->stage, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1486,10 +1441,8 @@ int dsl_device_pointers(dsl_handle* h, int buffer, const float** xyz, const int3
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;  // also drains the stream
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  CSoa3 a = buffer == DSL_BUF_POSITIONS ? cpos(h) : cvel(h);
-  xyz[0] = a.x;
-  xyz[1] = a.y;
-  xyz[2] = a.z;
+  const BufArrays a = buf_arrays(h, buffer);
+  for (int k = 0; k < 3; ++k) xyz[k] = a.a[k];
   if (ids) *ids = h->ids[h->cur_ids];
   if (n) *n = ncur;
   return DSL_OK;
@@ -1702,8 +1655,7 @@ int skin_alloc(dsl_handle* h) {
 int skin_enter(dsl_handle* h) {
   if (int rc = skin_alloc(h)) return rc;
   if (h->sort_scratch_dirty) {
-    HIP_TRY(h, hipMemsetAsync(h->cell_count, 0, sizeof(int) * (size_t)h->ncell_pad, h->stream));
-    if (h->unordered) HIP_TRY(h, hipMemsetAsync(h->unordered, 0, sizeof(unsigned int) * (size_t)(h->ncell_pad / 32), h->stream));
+    if (int rc = clean_sort_scratch(h)) return rc;
     h->sort_scratch_dirty = false;
   }
   if (int rc = set_cell_edge(h, h->c.h * (1.0f + h->skin), 3)) return rc;
@@ -1748,12 +1700,7 @@ int skin_step(dsl_handle* h) {
                        ordered ? h->cell_keys : nullptr, h->dcounter + 3, nullptr, 0, gate, h->ids[1], vX);
   });
   if (rc) return rc;
-  rc = timed(h, DSL_K_SCAN, [&] {
-    hipLaunchKernelGGL(k_scan_sums, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->cell_count, h->block_sums, h->dstats,
-                       h->n_tiles, gate);
-    hipLaunchKernelGGL(k_scan_apply, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->cell_count, h->block_sums,
-                       h->cell_start, h->dstats, gate);
-  });
+  rc = timed(h, DSL_K_SCAN, [&] { launch_scan(h, h->cell_count, h->block_sums, h->cell_start, h->dstats, h->n_tiles, gate); });
   if (rc) return rc;
   ScatterArrays a{};
   for (int k = 0; k < 6; ++k) {
@@ -1773,13 +1720,7 @@ int skin_step(dsl_handle* h) {
                          h->stream, c, a, so, pX, h->rank, h->cell_start, gate, vX, pRw);
   });
   if (rc) return rc;
-  rc = timed(h, DSL_K_TILE_LIST, [&] {
-    hipLaunchKernelGGL(k_tile_list, dim3(grid_for(h->tg.nlist)), dim3(kBlock), 0, h->stream, c, h->tg, h->cell_start, h->tiles,
-                       h->n_tiles, h->n_tiles + 5, nullptr, h->tile_desc_of, h->unordered, h->ncell_pad / 32, h->dcounter + 3,
-                       gate);
-    hipLaunchKernelGGL(k_tile_desc, dim3(std::min(h->tg.ntiles, 8192)), dim3(kWave), 0, h->stream, c, h->tg, h->cell_start,
-                       h->cell_start, h->tiles, h->n_tiles, h->tile_desc, nullptr, kTCap, gate);
-  });
+  rc = timed(h, DSL_K_TILE_LIST, [&] { launch_tile_tables(h, nullptr, gate); });
   if (rc) return rc;
   // candidates within h (1 + skin) of the sorted positions -> masks -> lists
   const double reach = 1.0 + (double)h->skin;
@@ -1807,19 +1748,13 @@ int skin_step(dsl_handle* h) {
   rc = timed(h, DSL_K_FORCE_INTEGRATE, [&] {
     dim3 g(persistent_grid(h, 2, true)), b(kLBlock);
     int* wql = walk_ctr_of(h, kSiteForceList);
-#define DSL_LAUNCH_FL2(GG, VV, QQ)                                                                                           \
-  hipLaunchKernelGGL((k_force_list<GG, VV, QQ>), g, b, 0, h->stream, c, h->tg, h->tile_desc_of, h->n_tiles, h->tile_desc,   \
-                     h->cell_start, st, pX, vX, pZ, vZ, pR, h->rho, h->pterm, h->lists, h->cap, po, vo, h->dstats, wql)
-#define DSL_LAUNCH_FL(GG, VV)                                             \
-  do {                                                                    \
-    if (wql != nullptr) DSL_LAUNCH_FL2(GG, VV, true);                     \
-    else DSL_LAUNCH_FL2(GG, VV, false);                                   \
-  } while (0)
-    if (G && V) DSL_LAUNCH_FL(true, true);
-    else if (G) DSL_LAUNCH_FL(true, false);
-    else DSL_LAUNCH_FL(false, true);
-#undef DSL_LAUNCH_FL
-#undef DSL_LAUNCH_FL2
+    with_flag(G, [&](auto fg) { with_flag(V, [&](auto fv) { with_flag(wql != nullptr, [&](auto fq) {
+      // (skin_usable admits no step without a force term: G = V = false has no list kernel, and would run the viscous one)
+      constexpr bool GG = decltype(fg)::value, VV = decltype(fv)::value || !GG;
+      hipLaunchKernelGGL((k_force_list<GG, VV, decltype(fq)::value>), g, b, 0, h->stream, c, h->tg, h->tile_desc_of, h->n_tiles,
+                         h->tile_desc, h->cell_start, st, pX, vX, pZ, vZ, pR, h->rho, h->pterm, h->lists, h->cap, po, vo, h->dstats,
+                         wql);
+    }); }); });
   });
   if (rc) return rc;
   h->cur_pv = Y;
@@ -2053,12 +1988,10 @@ int pci_begin_step(dsl_handle* h) {
   if (int rc = materialise_press(h)) return rc;
   CSoa3 p = cpos(h), v = cvel(h);
   Soa3 F = mfrc(h);
-  CSoa3 cF{F.x, F.y, F.z};
+  CSoa3 cF = as_const(F);
   const bool XS = pci_extra_terms(h);
   if (pci_tiled(h)) {
-    Soa3 G{h->gterm[0], h->gterm[1], h->gterm[2]};
-    Soa3 none{nullptr, nullptr, nullptr};
-    Soa3 xs{h->xsph[0], h->xsph[1], h->xsph[2]};
+    Soa3 G = mgterm(h), none = kNoSoa3, xs = mxsph(h);
     // ViscousAll :45 (+ cohesion, XSPH sums) and GradientPressureForce's term, which is the same in every
     // correction iteration: one sweep over the masks for both
     int rc = timed(h, DSL_K_VISCOUS, [&] {
@@ -2088,15 +2021,15 @@ int pci_iterate(dsl_handle* h) {
   dim3 g(grid_for(launch_n(h))), b(kBlock);
   CSoa3 p = cpos(h);
   Soa3 F = mfrc(h);
-  CSoa3 cF{F.x, F.y, F.z};
+  CSoa3 cF = as_const(F);
   Soa3 pp = mpcip(h), pvv = mpciv(h);
   const bool tiled = pci_tiled(h);
-  CSoa3 cpp{pp.x, pp.y, pp.z};
+  CSoa3 cpp = as_const(pp);
   if (!h->lsh && (h->pci_bin_mode > 0 || (h->pci_bin_mode == 0 && h->pci_binned))) {
     // the query points have left their particles (or the host asked for it): counting sort of the queries by their own
     // cells, then the sweep in that order (kernels_sph.hpp: k_pci_predict_bin)
     if (int rc = alloc_query_bins(h)) return rc;
-    CSoa3 cG{h->gterm[0], h->gterm[1], h->gterm[2]};
+    CSoa3 cG = as_const(mgterm(h));
     const bool qtiled = tiled && h->pci_qtiled;
     const bool rows = qtiled && h->pci_qpair && h->pci_qrows && h->qrows != nullptr;
     // rows kept inside a step: the first iteration fills them (and leaves the counts standing), the later ones move only
@@ -2121,10 +2054,7 @@ int pci_iterate(dsl_handle* h) {
           hipLaunchKernelGGL((k_pci_predict_bin<false, true, true, true>), g, b, 0, h->stream, c, bnd_of(h), p, pp, pvv, cG, F,
                              h->qcount, nullptr, nullptr, nullptr, h->dcounter + 4, h->build_seq, h->press, h->dstats, h->qrows,
                              kQueryRow, h->qrec, h->n_qtiles + 1, keep ? h->qslot : nullptr);
-        hipLaunchKernelGGL(k_qtile_list<true>, dim3(grid_for(h->tg.nlist)), dim3(kBlock), 0, h->stream, c, h->tg, h->qcount,
-                           h->qtiles, h->n_qtiles, h->dstats);
-        hipLaunchKernelGGL(k_tile_desc, dim3(std::min(h->tg.ntiles, 8192)), dim3(kWave), 0, h->stream, c, h->tg,
-                           h->cell_start, nullptr, h->qtiles, h->n_qtiles, h->qtile_desc, h->qcount, kTCap, SkinGate{nullptr}, keep);
+        launch_query_tile_tables(h, true, keep);
         return;
       }
       if (tiled)
@@ -2135,15 +2065,9 @@ int pci_iterate(dsl_handle* h) {
           hipLaunchKernelGGL((k_pci_predict_bin<true, false, decltype(fast)::value>), g, b, 0, h->stream, c, bnd_of(h), p, pp,
                              pvv, cG, F, h->qcount, h->rank, nullptr, nullptr, h->dcounter + 4, h->build_seq, h->press, h->dstats);
         });
-      hipLaunchKernelGGL(k_scan_sums, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->qcount, h->qsums, nullptr, nullptr);
-      hipLaunchKernelGGL(k_scan_apply, dim3(h->nscan), dim3(kBlock), 0, h->stream, h->qcount, h->qsums, h->qstart, nullptr);
+      launch_scan(h, h->qcount, h->qsums, h->qstart, nullptr, nullptr);
       hipLaunchKernelGGL(k_pci_query_scatter, g, b, 0, h->stream, c, cpp, h->rank, h->qstart, h->qrec, h->dstats);
-      if (qtiled) {  // the tiles that hold queries, and their tables
-        hipLaunchKernelGGL(k_qtile_list<false>, dim3(grid_for(h->tg.nlist)), dim3(kBlock), 0, h->stream, c, h->tg, h->qstart,
-                           h->qtiles, h->n_qtiles, h->dstats);
-        hipLaunchKernelGGL(k_tile_desc, dim3(std::min(h->tg.ntiles, 8192)), dim3(kWave), 0, h->stream, c, h->tg,
-                           h->cell_start, h->qstart, h->qtiles, h->n_qtiles, h->qtile_desc);
-      }
+      if (qtiled) launch_query_tile_tables(h, false, false);
     });
     if (rc) return rc;
     HIP_TRY(h, hipGetLastError());
@@ -2176,7 +2100,7 @@ int pci_iterate(dsl_handle* h) {
     return tiled ? DSL_OK : gradient_pass(h, 1);  // (tiled: F += the cached term went with the predictor)
   }
   if (tiled) {  // predict, DensityF + pressure, F += cached gradient term: one launch (kernels_tiled.hpp)
-    CSoa3 cG{h->gterm[0], h->gterm[1], h->gterm[2]};
+    CSoa3 cG = as_const(mgterm(h));
     return timed(h, DSL_K_PCI_DENSITY, [&] {
       hipLaunchKernelGGL(k_pci_density_tiled, dim3(persistent_grid(h, 4)), dim3(kTBlock), 0, h->stream, c, h->tg,
                          h->tile_desc_of, h->n_tiles, h->tile_desc, h->cell_start, bnd_of(h), p, pp, pvv, cG, F, h->press,
@@ -2371,18 +2295,12 @@ int slab_pack_on(dsl_handle* h, hipStream_t st, float width_full, float width, b
   const float* old_axis = nullptr;
   if (from_output) {  // band phase of the split step: integrated values are in the other half
     old_axis = h->c.slab_axis == 0 ? p.x : (h->c.slab_axis == 1 ? p.y : p.z);
-    Soa3 po = mpos(h, h->cur_pv ^ 1), vo = mvel(h, h->cur_pv ^ 1);
-    p = CSoa3{po.x, po.y, po.z};
-    v = CSoa3{vo.x, vo.y, vo.z};
+    p = as_const(mpos(h, h->cur_pv ^ 1));
+    v = as_const(mvel(h, h->cur_pv ^ 1));
   }
   const float* pa = h->c.slab_axis == 0 ? p.x : (h->c.slab_axis == 1 ? p.y : p.z);
   const int nblk = (h->cap + kPackChunk - 1) / kPackChunk;
-  CSoa3 pcip{nullptr, nullptr, nullptr}, pciv{nullptr, nullptr, nullptr};
-  if (h->pci_active) {  // migrants take their predictor state along
-    Soa3 a = mpcip(h), b = mpciv(h);
-    pcip = CSoa3{a.x, a.y, a.z};
-    pciv = CSoa3{b.x, b.y, b.z};
-  }
+  CSoa3 pcip = as_const(mpcip_if_active(h)), pciv = as_const(mpciv_if_active(h));  // migrants take their predictor state along
   hipLaunchKernelGGL(k_slab_count, dim3(nblk), dim3(kBlock), 0, st, h->c, sb, old_axis, pa, dev_lo ? 1 : 0,
                      dev_hi ? 1 : 0, h->pack_counts);
   hipLaunchKernelGGL(k_slab_offsets, dim3(1), dim3(kOffsBlock), 0, st, h->pack_counts, nblk, dev_lo, dev_hi, cap_full,
@@ -2455,11 +2373,7 @@ static int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const 
   if (!h->forces_uniform) return fail(h, DSL_ERR_INVALID, "dsl_slab_append: forces must be uniform (dsl_reset_forces)");
   if (cap_full + cap_xonly == 0) return DSL_OK;
   Soa3 p = mpos(h, h->cur_pv), v = mvel(h, h->cur_pv);
-  Soa3 pcip{nullptr, nullptr, nullptr}, pciv{nullptr, nullptr, nullptr};
-  if (h->pci_active) {
-    pcip = mpcip(h);
-    pciv = mpciv(h);
-  }
+  Soa3 pcip = mpcip_if_active(h), pciv = mpciv_if_active(h);
   hipLaunchKernelGGL(k_slab_append, dim3(grid_for(cap_full + cap_xonly), 2), dim3(kBlock), 0, h->stream, dev_message_a,
                      dev_message_b, cap_full, cap_xonly, h->dn, h->cap, p.x, p.y, p.z, v.x, v.y, v.z,
                      h->ids[h->cur_ids], h->dn + 5, dsl_slab_record_floats(h), pcip, pciv, h->c.slab_axis, shift_a, shift_b);
@@ -2777,13 +2691,19 @@ int link_append(dsl_handle* h) {
   return DSL_OK;
 }
 
+// the band selection into the link's send buffers, one per neighbour there is
+// (static: this block is inside extern "C", where the compiler exports even an unnamed namespace's functions by name)
+static int link_pack(dsl_handle* h, hipStream_t st, float width, bool from_output) {
+  SlabLink& L = *h->link;
+  return slab_pack_on(h, st, L.width_full, width, from_output, L.lo >= 0 ? L.send[0] : nullptr, L.hi >= 0 ? L.send[1] : nullptr,
+                      L.cap_full, L.cap_x);
+}
+
 // unsplit exchange on the handle's stream: pack, transfer, append
 int link_exchange(dsl_handle* h) {
   SlabLink& L = *h->link;
   if (L.lo < 0 && L.hi < 0) return DSL_OK;
-  if (int rc = slab_pack_on(h, h->stream, L.width_full, L.width, false, L.lo >= 0 ? L.send[0] : nullptr,
-                            L.hi >= 0 ? L.send[1] : nullptr, L.cap_full, L.cap_x))
-    return rc;
+  if (int rc = link_pack(h, h->stream, L.width, false)) return rc;
   if (int rc = link_post(h, h->stream)) return rc;
   return link_append(h);
 }
@@ -2852,22 +2772,14 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
     if (int rc = density_pass(h)) return rc;
     if (alone || !L.overlap) {
       // forces and integration of the owned particles (ghosts are marked for removal), band pack, transfer, append
+      // (a rank without neighbours exchanges nothing)
       if (int rc = force_integrate(h)) return rc;
-      if (!alone) {
-        if (int rc = slab_pack_on(h, h->stream, L.width_full, L.width, false, L.lo >= 0 ? L.send[0] : nullptr,
-                                  L.hi >= 0 ? L.send[1] : nullptr, L.cap_full, L.cap_x))
-          return rc;
-        if (int rc = link_post(h, h->stream)) return rc;
-        if (int rc = link_append(h)) return rc;
-        L.ghosts_in = true;
-      }
+      if (int rc = link_exchange(h)) return rc;
     } else {
       // band layers first; their pack and the RCCL transfer (side stream) run under the interior launch
       if (int rc = force_integrate(h, 1)) return rc;
       h->split_pending = true;
-      if (int rc = slab_pack_on(h, h->stream, L.width_full, h->split_width, true, L.lo >= 0 ? L.send[0] : nullptr,
-                                L.hi >= 0 ? L.send[1] : nullptr, L.cap_full, L.cap_x))
-        return rc;
+      if (int rc = link_pack(h, h->stream, h->split_width, true)) return rc;
       // the interior launch is queued BEHIND the pack and BEFORE the transfer is posted: the GPU goes straight from
       // the pack into it, the transfer kernels (side stream, behind the pack's event) join it
       HIP_TRY(h, hipEventRecord(L.ev_pack, h->stream));
@@ -2878,7 +2790,6 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
       HIP_TRY(h, hipEventRecord(L.ev_xfer, L.comm_stream));
       HIP_TRY(h, hipStreamWaitEvent(h->stream, L.ev_xfer, 0));
       if (int rc = link_append(h)) return rc;
-      L.ghosts_in = true;
     }
     h->steps++;
     L.steps++;

@@ -134,15 +134,16 @@ def _flipped(p, **kw):
 # ---- A: one force term without the other -----------------------------------------------------------------------------
 
 TERMS = [(1, 0), (0, 1)]
-PATHS = ["fast", "fast_skin", "exact", "fast_xsph", "exact_xsph"]
+PATHS = ["fast", "fast_skin", "exact", "fast_xsph", "exact_xsph", "fast_queue", "fast_skin_queue"]
 
 
 @pytest.mark.parametrize("path", PATHS)
 @pytest.mark.parametrize("G,V", TERMS)
 def test_one_force_term_without_the_other(G, V, path):
     """(pressure, viscosity) = (1, 0) and (0, 1) take instantiations of their own at every launch site: the FAST
-    tiled kernel (with and without the XSPH / cohesion variant), the skin step's list kernel, the EXACT tiled kernel.
-    10 steps of the 16^3 dam-break with seeded velocities."""
+    tiled kernel (with and without the XSPH / cohesion variant), the skin step's list kernel, the EXACT tiled kernel --
+    and the mask walk and the list walk once more with their tiles drawn from the tile queue (tile_queue = 2: the queue
+    is a template argument of both).  10 steps of the 16^3 dam-break with seeded velocities."""
     mode = EXACT if path.startswith("exact") else FAST
     p, pos = _scene(mode, G, V)
     vel = _seeded_vel(p)
@@ -158,9 +159,12 @@ def test_one_force_term_without_the_other(G, V, path):
         ora = _oracle(p, pos, vel, steps)
     # the term that is off must matter: the oracle with both terms on differs
     _guard(p, ora, _oracle(_flipped(p, wcsph_pressure_force=1, wcsph_viscosity=1), pos, vel, steps), steps)
-    eng = _engine(p, pos, vel, skin=0.1 if path == "fast_skin" else 0.0)
+    skin = path.startswith("fast_skin")
+    eng = _engine(p, pos, vel, skin=0.1 if skin else 0.0)
+    if path.endswith("queue"):
+        eng.set_option("tile_queue", 2)
     eng.wcsph_step(steps)
-    if path == "fast_skin":
+    if skin:
         assert eng.get_option("skin_steps") == steps and eng.get_option("skin_rebuilds") >= 2
         assert eng.get_option("skin_list_overflow") == 0
     else:

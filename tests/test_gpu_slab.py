@@ -19,7 +19,11 @@ pytestmark = pytest.mark.gpu
 STEPS = int(os.environ.get("DSL_SLAB_TEST_STEPS", "10"))  # (the variable: tools/slab_exact_diff.py looks for the first differing step)
 
 
-def _worker(rank, world, port, math_mode, n3, overlap, vscale, out, axis=2, native=False):
+def _force_terms(p, terms):
+    p.wcsph_pressure_force, p.wcsph_viscosity = terms
+
+
+def _worker(rank, world, port, math_mode, n3, overlap, vscale, out, axis=2, native=False, terms=(1, 1)):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -30,6 +34,7 @@ def _worker(rank, world, port, math_mode, n3, overlap, vscale, out, axis=2, nati
     from dieselfluid_amd.slab import SlabDriver
     SlabDriver.REPLAN_EVERY = 4  # exercise the message re-sizing inside the run
     drv = SlabDriver.dambreak(n3, math_mode=math_mode, device=0, axis=axis, overlap=overlap, native=native,
+                              params_hook=lambda p: _force_terms(p, terms),
                               vel_fn=lambda ids, pos: vscale * _vel_fn(ids, pos, axis=axis))
     assert drv.overlap == (overlap if overlap is not None else math_mode == 1)
     assert bool(getattr(drv, "native", False)) == native
@@ -51,11 +56,12 @@ def _worker(rank, world, port, math_mode, n3, overlap, vscale, out, axis=2, nati
     dist.destroy_process_group()
 
 
-def _single(n3, math_mode, vscale, steps=STEPS, shuffle=False, axis=2):
+def _single(n3, math_mode, vscale, steps=STEPS, shuffle=False, axis=2, terms=(1, 1)):
     """single-engine run; `shuffle` also re-orders the particles and moves the grid origin (other
     cells, other tiles, other tile-relative roundings in FAST mode): what a slab rank's own grid does"""
     from dieselfluid_amd import SPHEngine, scenes
     p, pos = scenes.dambreak_scene(n3, math_mode=math_mode)
+    _force_terms(p, terms)
     if shuffle:
         for a in range(3):
             p.grid_min[a] -= 0.37 * p.h
@@ -112,8 +118,21 @@ def _assert_identical(what, got_pos, got_vel, pos, vel):
     (1, True, 3, 24),
 ])
 def test_hip_slabs_match_single_engine(tmp_path, math_mode, overlap, world, n3):
+    _slabs_against_single(tmp_path, math_mode, overlap, world, n3)
+
+
+@pytest.mark.parametrize("terms", [(1, 0), (0, 1)], ids=["pressure_only", "viscosity_only"])
+@pytest.mark.parametrize("overlap", [False, True], ids=["unsplit", "split"])
+def test_hip_slabs_match_single_engine_with_one_force_term(tmp_path, overlap, terms):
+    """(pressure, viscosity) = (1, 0) and (0, 1) on slab ranks: the tiled force kernel's slab variant has instantiations
+    of its own for them, in the unsplit step and in the split step's band and interior launches.  The smallest case of
+    test_hip_slabs_match_single_engine, to its yardstick."""
+    _slabs_against_single(tmp_path, 1, overlap, 2, 16, terms)
+
+
+def _slabs_against_single(tmp_path, math_mode, overlap, world, n3, terms=(1, 1)):
     out = str(tmp_path / "slab_gpu.npz")
-    mp.spawn(_worker, args=(world, _free_port(), math_mode, n3, overlap, 1.0, out), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, _free_port(), math_mode, n3, overlap, 1.0, out, 2, False, terms), nprocs=world, join=True)
     z = np.load(out)
     info = z["info"]
     assert np.all(z["seen"] == 1)
@@ -122,7 +141,7 @@ def test_hip_slabs_match_single_engine(tmp_path, math_mode, overlap, world, n3):
     assert np.all(info[:, 2] == 0)          # no message / capacity overflow
     assert np.all(info[:, 3] == 0)          # split step: the margin held
     assert np.all(info[:, 5] != info[:, 4])  # messages were re-sized to the band occupancy
-    pos, vel = _single(n3, math_mode, 1.0)
+    pos, vel = _single(n3, math_mode, 1.0, terms=terms)
     if math_mode == 0:
         # EXACT: identical, not close -- to the single engine and to the single-domain oracle
         _assert_identical("the single engine", z["pos"], z["vel"], pos, vel)
@@ -133,9 +152,14 @@ def test_hip_slabs_match_single_engine(tmp_path, math_mode, overlap, world, n3):
     # particle populations of this scene amplify float32 rounding noise quickly; the yardstick is what
     # re-ordering the particles and moving the grid origin does to a single-engine run.  Slabs (own order
     # and own grid per rank) must stay within a small multiple.
-    pos_s, vel_s = _single(n3, math_mode, 1.0, shuffle=True)
+    pos_s, vel_s = _single(n3, math_mode, 1.0, shuffle=True, terms=terms)
     tol_x = max(4e-6, 5.0 * helpers.rel_err(pos_s, pos))
     tol_v = max(1e-4, 5.0 * helpers.rel_err(vel_s, vel))
+    if terms != (1, 1):
+        # the term that is off must matter: the single-domain oracle with both terms on is further away than the tolerance
+        both, one = _oracle_single(n3, 1.0), _oracle_single(n3, 1.0, params_hook=lambda p: _force_terms(p, terms))
+        dx, dv = helpers.rel_err(both[0], one[0]), helpers.rel_err(both[1], one[1])
+        assert dx > tol_x or dv > tol_v, (dx, dv)
     ex, ev = helpers.rel_err(z["pos"], pos), helpers.rel_err(z["vel"], vel)
     print(f"slab-vs-single x {ex:.2e} (tol {tol_x:.2e})  v {ev:.2e} (tol {tol_v:.2e})")
     assert ex < tol_x

@@ -28,6 +28,21 @@ def device_asm(extra_flags=()):
     return open(out).read()
 
 
+def kernel_names(asm: str):
+    """sorted mangled names of the kernels: the `_ZN3dsl...:` labels that have a `.amdhsa_kernel` entry"""
+    entries = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M))
+    return sorted(n for n in re.findall(r"^(_ZN3dsl\w+):", asm, re.M) if n in entries)
+
+
+def demangle(names):
+    """{mangled: readable}; the names themselves where no demangler is installed"""
+    tool = next((t for t in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "/usr/bin/c++filt") if os.path.exists(t)), None)
+    if tool is None or not names:
+        return {n: n for n in names}
+    out = subprocess.run([tool], input="\n".join(names), text=True, capture_output=True, check=True).stdout.splitlines()
+    return dict(zip(names, out))
+
+
 def unprotected_barriers(asm: str):
     """[(kernel, index, the instructions in front of the barrier)] for barriers without a drained LDS queue"""
     bad, total = [], 0
