@@ -504,6 +504,10 @@ const (
 	OptSkinPredict     = int(C.DSL_OPT_SKIN_PREDICT)
 	OptDeviceBytes     = int(C.DSL_OPT_DEVICE_BYTES)
 	OptGridOversub     = int(C.DSL_OPT_GRID_OVERSUB)
+	// the triangle-mesh collider: its size, the particles the last collide pass moved, the broad phase switch
+	OptColliderTriangles = int(C.DSL_OPT_COLLIDER_TRIANGLES)
+	OptCollideHits       = int(C.DSL_OPT_COLLIDE_HITS)
+	OptCollideCull       = int(C.DSL_OPT_COLLIDE_CULL)
 )
 
 // SetOption / GetOption: library options (DSL_OPT_* in include/dslsph.h), e.g. the neighbour-list skin of WCSPHStep.
@@ -646,4 +650,52 @@ func NewCommAll(devices []int) ([]*Comm, error) {
 		out[k] = &Comm{c: cs[k]}
 	}
 	return out, nil
+}
+
+// ---- geom.Collider on the device: Mesh.Collision (geom/mesh/mesh.go:41-57) for every fluid particle ----
+
+// SetColliderMesh hands T triangles (9 vertex floats and 3 normal floats each, in list order; the normals are used as
+// supplied) to the device; an empty list removes the collider.  While a mesh is set WCSPHStep and PCISPHStep run the
+// collide pass after Update.
+func (e *Engine) SetColliderMesh(vertices, normals []float32, radius, restitution float32) error {
+	if len(normals)%3 != 0 || len(vertices) != 3*len(normals) {
+		return errors.New("SetColliderMesh: 9 vertex floats and 3 normal floats per triangle")
+	}
+	if len(normals) == 0 {
+		return e.ck(C.dsl_collider_set_mesh(e.h, nil, nil, 0, C.float(radius), C.float(restitution)))
+	}
+	return e.ck(C.dsl_collider_set_mesh(e.h, (*C.float)(unsafe.Pointer(&vertices[0])), (*C.float)(unsafe.Pointer(&normals[0])), C.size_t(len(normals)/3), C.float(radius), C.float(restitution)))
+}
+
+// CollidePass: query + response for every fluid particle (asynchronous).
+func (e *Engine) CollidePass() error { return e.ck(C.dsl_collide_pass(e.h)) }
+
+// ColliderQuery: Mesh.Collision's returns for every fluid particle in host order, no response (blocking): the colliding
+// triangle's index or -1, its normal, the barycentric coordinates, the rewound position.
+func (e *Engine) ColliderQuery() (tri []int32, normal, coord, point []float32, err error) {
+	n := int(e.Params.n_particles)
+	tri = make([]int32, n)
+	normal, coord, point = make([]float32, 3*n), make([]float32, 3*n), make([]float32, 3*n)
+	err = e.ColliderQueryInto(tri, normal, coord, point)
+	return
+}
+
+// ColliderQueryInto: ColliderQuery into the caller's slices (N, 3N, 3N, 3N long); a nil slice is a result the caller
+// does not want: it is neither computed into a buffer nor downloaded (the C call's NULL pointer).
+func (e *Engine) ColliderQueryInto(tri []int32, normal, coord, point []float32) error {
+	n := int(e.Params.n_particles)
+	if (tri != nil && len(tri) != n) || (normal != nil && len(normal) != 3*n) || (coord != nil && len(coord) != 3*n) || (point != nil && len(point) != 3*n) {
+		return errors.New("ColliderQueryInto: tri holds N, normal, coord and point 3 N values (or are nil)")
+	}
+	fp := func(s []float32) *C.float {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.float)(unsafe.Pointer(&s[0]))
+	}
+	var tp *C.int32_t
+	if len(tri) != 0 {
+		tp = (*C.int32_t)(unsafe.Pointer(&tri[0]))
+	}
+	return e.ck(C.dsl_collider_query(e.h, tp, fp(normal), fp(coord), fp(point)))
 }

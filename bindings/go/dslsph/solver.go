@@ -11,6 +11,32 @@ const (
 	SPH_THREAD_WAITING = 104
 )
 
+// Mesh is the part of mesh.Mesh (geom/mesh/mesh.go:11-14) a collider needs: three vertices per triangle and one normal
+// per triangle, as mesh.InitMesh leaves them.
+type Mesh struct {
+	Vertexes [][3]float32
+	Normals  [][3]float32
+}
+
+// SetColliders hands the collider list of sph.Init (model/sph/fluid.go:28,41) to the engine: the meshes' triangles
+// concatenated in list order, queried with radius r; e is the response's restitution.  An empty list removes them.
+func SetColliders(core *Engine, colliders []Mesh, r, e float32) error {
+	var verts, normals []float32
+	for _, m := range colliders {
+		for t := 0; t < len(m.Vertexes)/3; t++ {
+			for k := 0; k < 3; k++ {
+				verts = append(verts, m.Vertexes[3*t+k][:]...)
+			}
+			n := [3]float32{}
+			if t < len(m.Normals) {
+				n = m.Normals[t]
+			}
+			normals = append(normals, n[:]...)
+		}
+	}
+	return core.SetColliderMesh(verts, normals, r, e)
+}
+
 // WCSPH implements solver.SPHMethod (solver/method.go:3-6) like wcsph.WCSPH
 // (solver/wcsph/wcsph.go:9-75); unlike the reference type it can be constructed.
 type WCSPH struct{ core *Engine }

@@ -98,6 +98,9 @@ EXPORTS = {
     "dsl_wcsph_step": (C.c_int, [_vp, C.c_int]),
     "dsl_pcisph_begin": (C.c_int, [_vp]),
     "dsl_pcisph_step": (C.c_int, [_vp, C.c_int]),
+    "dsl_collider_set_mesh": (C.c_int, [_vp, _fp, _fp, C.c_size_t, C.c_float, C.c_float]),
+    "dsl_collide_pass": (C.c_int, [_vp]),
+    "dsl_collider_query": (C.c_int, [_vp, _ip, _fp, _fp, _fp]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),
@@ -166,7 +169,8 @@ def build_library(force: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise DslError("hipcc not found: cannot build libdslsph.so (no fallback exists)")
     os.makedirs(os.path.dirname(_BUILT), exist_ok=True)
-    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT, os.path.join(_SRC_DIR, "dslsph.hip")]
+    # two translation units: the engine, and the triangle-mesh collider's kernels (csrc/collide.hip)
+    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in ("dslsph.hip", "collide.hip")]
     subprocess.check_call(cmd)
     return _BUILT
 

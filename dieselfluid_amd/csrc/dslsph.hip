@@ -31,6 +31,7 @@
 #include "kernels_lsh.hpp"
 #include "kernels_tiled.hpp"
 #include "kernels_skin.hpp"
+#include "collide.hpp"
 
 struct SlabLink;
 
@@ -170,6 +171,14 @@ struct dsl_handle {
   int tile_queue = 1;  // 0 never, 1 from 8M particles on, 2 always (tests)
   int* walk_ctr = nullptr;
   int walk_parity[16] = {};
+  // triangle-mesh collider (kernels_collide.hpp; dsl_collider_set_mesh): col_tri = 0: none, nothing is launched
+  int col_tri = 0, col_alloc = 0;
+  float col_radius = 0.0f, col_rest = 0.0f, col_s_thr = -1.0f;
+  bool col_cull = true;
+  TriRec* col_rec = nullptr;
+  TriBox *col_box = nullptr, *col_chunk = nullptr;
+  int* col_hits = nullptr;    // particles the last collide pass moved
+  float* col_query = nullptr; // dsl_collider_query's staging: tri, normal, coord, point in host order (10 words per particle)
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hpp)
   // timing
@@ -863,6 +872,24 @@ int update_pass(dsl_handle* h, bool use_xs = false) {
   return DSL_OK;
 }
 
+// The collider pass (kernels_collide.hpp): Mesh.Collision for every fluid particle, then the build-defined response, in
+// place on the current state.  Without a mesh nothing is launched.  dsl_stats.max_vel / max_f stay what Update saw.
+ColMesh col_mesh(const dsl_handle* h) {
+  return ColMesh{h->col_rec, h->col_box, h->col_chunk, h->col_tri, h->col_s_thr, h->col_rest, h->col_cull ? 1 : 0};
+}
+int collide_pass(dsl_handle* h) {
+  if (h->col_tri == 0) return DSL_OK;
+  HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
+  int rc = timed(h, DSL_K_COLLIDE, [&] {
+    launch_collide(h->stream, true, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), ColQuery{},
+                   h->col_hits);
+  });
+  if (rc) return rc;
+  h->grid_valid = false;  // positions moved
+  h->masks_valid = false;
+  return DSL_OK;
+}
+
 // exact live count on the host (slab mode: one small device read)
 int host_count(dsl_handle* h, int* out) {
   if (!h->c.n_ptr) {
@@ -954,6 +981,11 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->lsh_len);
   (void)hipFree(h->lsh_samples);
   (void)hipFree(h->nmask);
+  (void)hipFree(h->col_rec);
+  (void)hipFree(h->col_box);
+  (void)hipFree(h->col_chunk);
+  (void)hipFree(h->col_hits);
+  (void)hipFree(h->col_query);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1636,6 +1668,7 @@ constexpr int kSkinRetry = 2048;
 
 bool skin_usable(const dsl_handle* h) {
   return h->skin > 0.0f && h->steps >= h->skin_retry_at && h->prm.math_mode == DSL_MATH_FAST && !h->lsh && h->c.slab_axis < 0 && !h->c.n_ptr && h->nb == 0 &&
+         h->col_tri == 0 &&  // (the collide pass moves particles behind the kernel that measures displacement)
          !h->pci_active && h->c.xsph_eps == 0.0f && h->c.st_kappa == 0.0f && use_tiled(h) && h->nmask != nullptr &&
          (h->c.wcsph_pressure_force != 0 || h->c.wcsph_viscosity != 0);
 }
@@ -1811,6 +1844,7 @@ int dsl_wcsph_step(dsl_handle* h, int nsteps) {
     if (int rc = build_grid(h, false)) return rc;  // NN(): geometric neighbour rule -> every step
     if (int rc = density_pass(h)) return rc;        // DensityAll   wcsph.go:18
     if (int rc = force_integrate(h)) return rc;     // ExternalAll, PressureAll, Update wcsph.go:19-21
+    if (int rc = collide_pass(h)) return rc;        // (only while a collider mesh is set)
     h->steps++;
   }
   return DSL_OK;
@@ -1867,6 +1901,7 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
       h->pci_qincr = value != 0.0;
       h->pci_rows_live = false;
       return DSL_OK;
+    case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
     default:
       return fail(h, DSL_ERR_INVALID, "dsl_set_option: unknown or read-only option");
   }
@@ -1903,8 +1938,113 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_GRID_OVERSUB: *value = (double)h->grid_oversub; return DSL_OK;
     case DSL_OPT_TILE_QUEUE: *value = (double)h->tile_queue; return DSL_OK;
     case DSL_OPT_PCI_QINCR: *value = h->pci_qincr ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDER_TRIANGLES: *value = (double)h->col_tri; return DSL_OK;
+    case DSL_OPT_COLLIDE_CULL: *value = h->col_cull ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDE_HITS: {  // (blocking: the kernel counts on the device)
+      int hits = 0;
+      if (h->col_hits) {
+        HIP_TRY(h, hipMemcpyAsync(&hits, h->col_hits, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+      }
+      *value = (double)hits;
+      return DSL_OK;
+    }
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// triangle-mesh collider (kernels_collide.hpp)
+// ---------------------------------------------------------------------------------------
+int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* normals, size_t n_triangles, float radius,
+                          float restitution) {
+  CHECK_HANDLE(h);
+  if (h->c.slab_axis >= 0 || h->c.n_ptr)
+    return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_set_mesh: a collider mesh is not supported in slab mode");
+  if (n_triangles == 0) {  // removes the mesh (the arrays stay for the next one)
+    h->col_tri = 0;
+    return DSL_OK;
+  }
+  if (!vertices || !normals) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: null vertex or normal pointer");
+  if (n_triangles > ((size_t)1 << 24)) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: more than 2^24 triangles");
+  const int T = (int)n_triangles, nchunk = (T + kColChunk - 1) / kColChunk;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the mesh that is replaced)
+  h->col_tri = 0;  // no mesh until the new one is whole: a failure below leaves the handle without a collider
+  if (T > h->col_alloc) {
+    (void)hipFree(h->col_rec);
+    (void)hipFree(h->col_box);
+    (void)hipFree(h->col_chunk);
+    h->col_rec = nullptr;
+    h->col_box = h->col_chunk = nullptr;
+    h->col_alloc = 0;
+    int rc = DSL_OK;
+    if ((rc = dev_alloc(h, &h->col_rec, (size_t)T))) return rc;
+    if ((rc = dev_alloc(h, &h->col_box, (size_t)T))) return rc;
+    if ((rc = dev_alloc(h, &h->col_chunk, (size_t)nchunk))) return rc;
+    h->col_alloc = T;
+  }
+  if (!h->col_hits)
+    if (int rc = dev_alloc(h, &h->col_hits, 1)) return rc;
+  float* in = nullptr;  // the caller's arrays: 9 T vertices, then 3 T normals
+  if (hipMalloc((void**)&in, (size_t)12 * T * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, DSL_ERR_NOMEM, "dsl_collider_set_mesh: hipMalloc failed");
+  }
+  hipError_t e = hipMemcpyAsync(in, vertices, (size_t)9 * T * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(in + (size_t)9 * T, normals, (size_t)3 * T * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    launch_collide_prep(h->stream, T, in, in + (size_t)9 * T, radius, h->col_rec, h->col_box, h->col_chunk);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (host pointers are never retained after a call returns)
+  (void)hipFree(in);
+  if (e != hipSuccess) return fail(h, DSL_ERR_DEVICE, std::string("dsl_collider_set_mesh: ") + hipGetErrorString(e));
+  // `Mag(q) <= r` on the float32 sum of squares: Mag is float32(sqrt(float64(s))) (vector.go:301-308), monotone in s, so
+  // the test is s <= the largest float whose Mag is <= r.  None for a negative or NaN radius (s >= 0 or NaN: -1 fails all).
+  float thr = -1.0f;
+  if (radius >= 0.0f) {
+    auto mag = [](float s) { return (float)std::sqrt((double)s); };
+    thr = radius * radius;
+    if (!(thr <= 3.4028235e38f)) thr = 3.4028235e38f;
+    while (thr > 0.0f && mag(thr) > radius) thr = std::nextafter(thr, 0.0f);
+    while (thr < INFINITY && mag(std::nextafter(thr, INFINITY)) <= radius) thr = std::nextafter(thr, INFINITY);
+  }
+  h->col_s_thr = thr;
+  h->col_radius = radius;
+  h->col_rest = restitution;
+  h->col_tri = T;
+  return DSL_OK;
+}
+
+int dsl_collide_pass(dsl_handle* h) {
+  CHECK_HANDLE(h);
+  return collide_pass(h);
+}
+
+int dsl_collider_query(dsl_handle* h, int32_t* tri, float* normal, float* coord, float* point) {
+  CHECK_HANDLE(h);
+  if (h->c.n_ptr) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_query: not available in slab mode");
+  if (h->ids_global) return fail(h, DSL_ERR_INVALID, "dsl_collider_query: host order is gone after dsl_set_ids");
+  const size_t nf = (size_t)n_fluid_of(h);
+  if (h->col_tri == 0) {  // Mesh.Collision of an empty mesh: no collision, empty vectors (mesh.go:56)
+    if (tri) std::fill(tri, tri + nf, -1);
+    for (float* a : {normal, coord, point})
+      if (a) std::fill(a, a + 3 * nf, 0.0f);
+    return DSL_OK;
+  }
+  if (!h->col_query)
+    if (int rc = dev_alloc(h, &h->col_query, (size_t)10 * h->cap)) return rc;
+  float* qb = h->col_query;
+  const ColQuery q{tri ? reinterpret_cast<int*>(qb) : nullptr, normal ? qb + nf : nullptr, coord ? qb + 4 * nf : nullptr,
+                   point ? qb + 7 * nf : nullptr, h->ids[h->cur_ids]};
+  launch_collide(h->stream, false, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), q, nullptr);
+  HIP_TRY(h, hipGetLastError());
+  if (tri) HIP_TRY(h, hipMemcpyAsync(tri, q.tri, nf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (normal) HIP_TRY(h, hipMemcpyAsync(normal, q.normal, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (coord) HIP_TRY(h, hipMemcpyAsync(coord, q.coord, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (point) HIP_TRY(h, hipMemcpyAsync(point, q.point, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DSL_OK;
 }
 
 int dsl_pcisph_begin(dsl_handle* h) {
@@ -2131,6 +2271,7 @@ int pci_check(dsl_handle* h) {                   // :95-98
 
 int pci_end_step(dsl_handle* h) {                // Update :101 (positions advect with v + XSPH)
   if (int rc = update_pass(h, pci_extra_terms(h))) return rc;
+  if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set)
   h->steps++;
   h->pci_steps++;
   return DSL_OK;
@@ -2203,6 +2344,7 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (axis < -1 || axis > 2 || !(lo < hi)) return fail(h, DSL_ERR_INVALID, "dsl_slab_config: bad axis or empty range");
   if (h->lsh) return fail(h, DSL_ERR_UNSUPPORTED, "lsh_ref buckets are angular cones through the whole domain: no slabs");
   if (axis >= 0 && h->nb > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: boundary particles are not supported in slab mode");
+  if (axis >= 0 && h->col_tri > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;

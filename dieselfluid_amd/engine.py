@@ -21,7 +21,7 @@ _COMPS = {0: 3, 1: 3, 2: 3, 3: 1, 4: 1, 5: 3, 6: 3}
 KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
-    "neigh_lists": 13,
+    "neigh_lists": 13, "collide": 14,
 }
 
 
@@ -433,6 +433,30 @@ class SPHEngine:
     def force_pass(self):
         self._ck(self._L.dsl_force_pass(self._h))
 
+    # -- geom.Collider: Mesh.Collision (geom/mesh/mesh.go:41-57) -------------------
+    def set_collider_mesh(self, vertices=None, normals=None, radius: float = 0.0, restitution: float = 0.0):
+        """T triangles in list order: vertices (T, 3, 3), normals (T, 3), used as supplied.  Several meshes: concatenate
+        them.  None or an empty array removes the mesh."""
+        v = np.ascontiguousarray(vertices if vertices is not None else [], dtype=np.float32).reshape(-1)
+        nrm = np.ascontiguousarray(normals if normals is not None else [], dtype=np.float32).reshape(-1)
+        if v.size % 9 or nrm.size * 3 != v.size:
+            raise DslError("set_collider_mesh: 9 vertex floats and 3 normal floats per triangle")
+        self._ck(self._L.dsl_collider_set_mesh(self._h, _fp(v), _fp(nrm), v.size // 9, C.c_float(radius),
+                                               C.c_float(restitution)))
+
+    def collide(self):
+        """query + response for every fluid particle (the step drivers run it themselves while a mesh is set)"""
+        self._ck(self._L.dsl_collide_pass(self._h))
+
+    def collider_query(self):
+        """Mesh.Collision for every fluid particle, no response: (tri, normal, coord, point) in host order"""
+        n = self.n_fluid
+        tri = np.empty(n, dtype=np.int32)
+        nrm, coord, point = (np.empty((n, 3), dtype=np.float32) for _ in range(3))
+        self._ck(self._L.dsl_collider_query(self._h, tri.ctypes.data_as(C.POINTER(C.c_int32)), _fp(nrm), _fp(coord),
+                                            _fp(point)))
+        return tri, nrm, coord, point
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -484,7 +508,8 @@ class SPHEngine:
     # library options (include/dslsph.h: DSL_OPT_*)
     OPTIONS = {"skin": 1, "skin_steps": 2, "skin_rebuilds": 3, "skin_list_overflow": 4, "skin_suspensions": 5, "device_bytes": 6, "skin_fields_own": 7, "skin_fields_padded": 8, "skin_predict": 9, "skin_tau_steps": 10,
                "density_pair": 16, "cell_keys": 17, "tile_box": 18, "persistent_blocks": 19, "pci_qtiled": 20,
-               "pci_qpair": 21, "pci_qrows": 22, "pci_qincr": 23, "list_build": 24, "grid_oversub": 25, "tile_queue": 26}
+               "pci_qpair": 21, "pci_qrows": 22, "pci_qincr": 23, "list_build": 24, "grid_oversub": 25, "tile_queue": 26,
+               "collider_triangles": 32, "collide_hits": 33, "collide_cull": 34}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

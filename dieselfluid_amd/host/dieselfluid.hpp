@@ -10,6 +10,7 @@
 //
 // Mirrors (file:line in the dieselfluid repository):
 //   dsl::sph::SPH                 model/sph/fluid.go:23-277
+//   dsl::mesh::Mesh / InitMesh    geom/mesh/mesh.go:11-76, geom/triangle/tri.go:37-101 (Collision: one point, on the host)
 //   dsl::solver::SPHMethod        solver/method.go:3-6
 //   dsl::solver::WCSPH            solver/wcsph/wcsph.go:9-75
 //   dsl::solver::PciMethod        solver/pcisph/pcisph_darwin.go:11-118
@@ -124,10 +125,30 @@ inline std::vector<float> LatticePositions(int n3, const float* origin, int orig
 
 }  // namespace sph
 
-// geom/mesh/mesh.go: the part of Mesh the SPH path touches
+// geom/mesh/mesh.go: the part of Mesh the SPH path touches.  Host arithmetic is float32 in the reference's operation
+// order (vector.go: Dot :268-276, Cross :283-297, Mag :301-308, Norm :322-331), like the lattice above.
 namespace mesh {
+using Vec = std::array<float, 3>;
+inline float Dot(const Vec& a, const Vec& b) {
+  const float t0 = a[0] * b[0], t1 = a[1] * b[1], t2 = a[2] * b[2];
+  return (t0 + t1) + t2;
+}
+inline float Mag(const Vec& v) { return (float)std::sqrt((double)Dot(v, v)); }
+inline Vec Sub(const Vec& b, const Vec& a) { return {b[0] - a[0], b[1] - a[1], b[2] - a[2]}; }
+inline Vec Add(const Vec& a, const Vec& b) { return {a[0] + b[0], a[1] + b[1], a[2] + b[2]}; }
+inline Vec Scale(const Vec& a, float k) { return {a[0] * k, a[1] * k, a[2] * k}; }
+
+// Mesh.Collision's four returns (mesh.go:41): normal, barycentric coordinates, collision point, collision; `tri` is the
+// index of the colliding triangle (-1: none), which dsl_collider_query returns as well
+struct CollisionResult {
+  Vec normal{0.f, 0.f, 0.f}, coord{0.f, 0.f, 0.f}, point{0.f, 0.f, 0.f};
+  bool collision = false;
+  int tri = -1;
+};
+
 struct Mesh {
-  std::vector<std::array<float, 3>> Vertexes;
+  std::vector<Vec> Vertexes;
+  std::vector<Vec> Normals;  // one per triangle (mesh.go:13,20)
   // mesh.go:60-76: one particle per vertex (`density` is unused there too); the bound check
   // `x < len(particle_list)-3` leaves the LAST vertex's particle at the origin
   std::vector<float> GenerateBoundaryParticles(float /*density*/) const {
@@ -143,7 +164,66 @@ struct Mesh {
     }
     return particle_list;
   }
+
+  // Mesh.Collision (mesh.go:41-57) through Triangle.BarycentricCollision / Barycentric (tri.go:37-101) for ONE point on
+  // the host: the same query dsl_collider_query answers for every particle on the device, operation for operation.
+  CollisionResult Collision(const Vec& P, const Vec& V, double dt, float r) const {
+    CollisionResult out;
+    if (Mag(V) == 0.0f) return out;  // tri.go:39, for every triangle alike
+    const int VERTS = (int)Vertexes.size();
+    for (int i = 0; i + 2 < VERTS; i += 3) {
+      const Vec& n = Normals[(size_t)i / 3];
+      const Vec &a = Vertexes[(size_t)i], &b = Vertexes[(size_t)i + 1], &c = Vertexes[(size_t)i + 2];
+      float nDotRay = Dot(n, V);
+      if (nDotRay == 0.0f) nDotRay = 0.0001f;
+      const float d = Dot(Sub(a, P), n);
+      const float k = d / nDotRay;
+      const Vec p0 = Add(P, Scale(V, k));
+      const float dist = Mag(Sub(P, p0));
+      if (!(dist <= r)) continue;
+      const Vec v0 = Sub(b, a), v1 = Sub(c, a), v2 = Sub(P, a);  // Barycentric, tri.go:79-101
+      const float d00 = Dot(v0, v0), d01 = Dot(v0, v1), d11 = Dot(v1, v1), d20 = Dot(v2, v0), d21 = Dot(v2, v1);
+      const float q0 = d00 * d11, q1 = d01 * d01;
+      const float denom = q0 - q1;
+      const float a0 = d11 * d20, a1 = d01 * d21, b0 = d00 * d21, b1 = d01 * d20;
+      const float u = (a0 - a1) / denom;
+      const float v = (b0 - b1) / denom;
+      const float w = (1.0f - v) - u;
+      const float sum = (u + v) + w;
+      if (u <= 1.0f && v <= 1.0f && w <= 1.0f && sum <= 1.0f && u >= 0.0f && v >= 0.0f && w >= 0.0f) {
+        out.normal = n;
+        out.coord = {u, v, w};
+        out.point = Add(P, Scale(V, -1.0f * (float)dt));  // tri.go:70
+        out.collision = true;
+        out.tri = i / 3;
+        return out;  // the first triangle in list order (mesh.go:50-52)
+      }
+    }
+    return out;
+  }
 };
+
+// mesh.InitMesh (mesh.go:17-37), its two quirks included: the loop stops at `i < len(vertices)-3`, so the LAST
+// triangle's normal stays the zero vector; and the flip towards `origin` is computed and thrown away (vector.Scale
+// returns a new vector, mesh.go:30), so the sign of a normal means nothing.
+inline Mesh InitMesh(const std::vector<Vec>& vertices, const Vec& origin) {
+  Mesh nMesh;
+  nMesh.Vertexes = vertices;
+  nMesh.Normals.assign(vertices.size() / 3, Vec{0.f, 0.f, 0.f});
+  for (int i = 0; i < (int)vertices.size() - 3; i += 3) {
+    const Vec e0 = Sub(vertices[(size_t)i + 1], vertices[(size_t)i]), e1 = Sub(vertices[(size_t)i + 2], vertices[(size_t)i]);
+    const float c0a = e0[1] * e1[2], c0b = e0[2] * e1[1], c1a = e0[2] * e1[0], c1b = e1[2] * e0[0], c2a = e0[0] * e1[1],
+                c2b = e1[0] * e0[1];
+    const Vec N{c0a - c0b, c1a - c1b, c2a - c2b};  // Cross
+    Vec n{0.f, 0.f, 0.f};                         // Norm: the zero vector stays zero
+    const float l = Mag(N);
+    if (l != 0.0f) n = {N[0] / l, N[1] / l, N[2] / l};
+    const float dv0 = Dot(n, Sub(vertices[(size_t)i], origin));
+    if (dv0 > 0.0f) (void)Scale(n, -1.0f);  // (dropped, as in the reference)
+    nMesh.Normals[(size_t)i / 3] = n;
+  }
+  return nMesh;
+}
 }  // namespace mesh
 
 namespace sph {
@@ -151,7 +231,8 @@ namespace sph {
 class SPH {
  public:
   // sph.Init(scl, origin, colliders, n3, pci)  fluid.go:41-88.  `colliders` is accepted and
-  // ignored exactly as the reference does (BoundaryParticles is commented out, fluid.go:70);
+  // ignored exactly as the reference does (BoundaryParticles is commented out, fluid.go:70; Colliders() below
+  // hands a list to the device);
   // `boundary_capacity` reserves device slots for a later BoundaryParticles() call.
   static SPH Init(float scl, const std::vector<float>& origin, const std::vector<mesh::Mesh*>* colliders, int n3, bool pci,
                   int device = 0, int math_mode = DSL_MATH_EXACT, int boundary_capacity = 0) {
@@ -217,6 +298,23 @@ class SPH {
     return colliderPositions;
   }
   int Total() const { return particles_ + boundary_; }  // particle_array.go:134-136
+
+  // The collider list of sph.Init (fluid.go:28,41) handed to the device: the meshes' triangles and normals concatenated in
+  // list order (Mesh.Collision per mesh in list order is Mesh.Collision of the concatenation), queried with radius r;
+  // `e` is the build-defined response's restitution.  An empty list removes the collider.  From then on the step
+  // drivers run the collide pass after Update (include/dslsph.h: dsl_collider_set_mesh).
+  void Colliders(const std::vector<mesh::Mesh*>& meshes, float r, float e) {
+    std::vector<float> verts, normals;
+    for (const mesh::Mesh* m : meshes) {
+      const size_t T = m->Vertexes.size() / 3;
+      for (size_t k = 0; k < 3 * T; ++k) verts.insert(verts.end(), m->Vertexes[k].begin(), m->Vertexes[k].end());
+      for (size_t t = 0; t < T; ++t) {
+        const mesh::Vec n = t < m->Normals.size() ? m->Normals[t] : mesh::Vec{0.f, 0.f, 0.f};
+        normals.insert(normals.end(), n.begin(), n.end());
+      }
+    }
+    ck(dsl_collider_set_mesh(h_, verts.data(), normals.data(), normals.size() / 3, r, e));
+  }
 
   int N() const { return particles_; }                 // fluid.go:106-108
   void NN() { ck(dsl_build_neighbours(h_)); }          // fluid.go:100-102

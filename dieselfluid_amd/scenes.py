@@ -147,3 +147,49 @@ def dambreak_scene(n3: int, *, h_over_dx: float = 2.0, jitter: float = 0.05, see
     p.math_mode = math_mode
     pos = dambreak_positions(n3, dx, jitter, seed) if positions else None
     return p, pos
+
+
+def quad_mesh(p0, p1, p2, p3, normal, subdiv: int = 1):
+    """(vertices (T, 3, 3), normals (T, 3)), float32: the quad p0 p1 p2 p3 (corners in order around it) as 2 * subdiv^2
+    triangles with `normal` on every one -- as supplied: a collider's normals are neither normalised nor checked
+    (SPHEngine.set_collider_mesh)."""
+    c = [np.asarray(q, dtype=np.float64) for q in (p0, p1, p2, p3)]
+    s = int(subdiv)
+
+    def at(i, j):  # bilinear
+        u, v = i / s, j / s
+        return (1 - u) * (1 - v) * c[0] + u * (1 - v) * c[1] + u * v * c[2] + (1 - u) * v * c[3]
+
+    tris = []
+    for i in range(s):
+        for j in range(s):
+            a, b, cc, d = at(i, j), at(i + 1, j), at(i + 1, j + 1), at(i, j + 1)
+            tris.append((a, b, cc))
+            tris.append((a, cc, d))
+    verts = np.asarray(tris, dtype=f32).reshape(-1, 3, 3)
+    normals = np.tile(np.asarray(normal, dtype=f32).reshape(1, 3), (verts.shape[0], 1))
+    return verts, normals
+
+
+def box_mesh(center, size, subdiv: int = 1):
+    """(vertices, normals) of an axis-aligned box obstacle: six faces of 2 * subdiv^2 triangles each (12, 192, 3072
+    triangles for subdiv 1, 4, 16), unit outward normals."""
+    ctr = np.asarray(center, dtype=np.float64)
+    half = 0.5 * np.asarray(size, dtype=np.float64)
+    vs, ns = [], []
+    for axis in range(3):
+        a1, a2 = (axis + 1) % 3, (axis + 2) % 3
+        for sign in (-1.0, 1.0):
+            corners = []
+            for s1, s2 in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
+                q = ctr.copy()
+                q[axis] += sign * half[axis]
+                q[a1] += s1 * half[a1]
+                q[a2] += s2 * half[a2]
+                corners.append(q)
+            nrm = np.zeros(3)
+            nrm[axis] = sign
+            v, n = quad_mesh(*corners, nrm, subdiv)
+            vs.append(v)
+            ns.append(n)
+    return np.concatenate(vs), np.concatenate(ns)

@@ -150,7 +150,8 @@ enum {
   DSL_K_PCI_DENSITY = 11,
   DSL_K_TILE_LIST = 12, /* non-empty 4x4x4-cell tiles for the LDS-tiled kernels */
   DSL_K_NEIGH_LISTS = 13, /* skin step: wide candidate sweep + neighbour lists (rebuild steps only) */
-  DSL_K_COUNT = 14
+  DSL_K_COLLIDE = 14,     /* triangle-mesh collider: query + response (only while a mesh is set) */
+  DSL_K_COUNT = 15
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -276,6 +277,35 @@ int dsl_pcisph_error_word(dsl_handle *h, uint32_t *dev_word, int store);
  * neighbours that live on another rank.  Any of the three pointers may be NULL. */
 int dsl_pcisph_set_binning(dsl_handle *h, int mode);
 int dsl_pcisph_get_binning(dsl_handle *h, int *mode, int *active, int *escaped);
+
+/* geom.Collider (geom/interfaces.go:11-16) as Mesh.Collision implements it (geom/mesh/mesh.go:41-57) through
+ * Triangle.BarycentricCollision / Barycentric (geom/triangle/tri.go:37-101): the reference takes a list of colliders in
+ * sph.Init (model/sph/fluid.go:28,41) and defines the query; nothing in it consumes the result.
+ * A collider is T triangles in list order: vertices a,b,c (9 floats) and one normal n (3 floats) each.  The normal is
+ * used as supplied -- not normalised, flipped or checked (InitMesh leaves the last one zero and throws its flip away,
+ * mesh.go:24,30).  Several meshes: the host concatenates them in list order.
+ * The query for a fluid particle is Mesh.Collision(P, V, dt = dsl_params.dt, r = radius): the FIRST triangle in list order
+ * that collides wins; a particle with Mag(V) == 0 never collides.  The arithmetic is the reference's, float32 rounded once
+ * per operation, and the SAME in DSL_MATH_EXACT and DSL_MATH_FAST (results are bit-identical between the two: a
+ * collision is a classification).  Returns per particle: the triangle index (-1: none), its normal, the barycentric
+ * coordinates (u,v,w), and point = P + V * (-dt), the position rewound (tri.go:70); zeros where nothing collides.
+ * Response (build-defined, like the wall box): a colliding particle with k = ((a - P).n) / (n.V) >= 0 -- the plane lies
+ * ahead along V -- is set back to `point` and v <- v - n * ((1 + restitution) * (v.n)); a receding one (k < 0) is left
+ * alone.  Boundary particles are not queried; the PCISPH predictor state is not touched.
+ * dsl_collider_set_mesh : T = 0 removes the mesh.  Blocking.  Not available in slab mode (DSL_ERR_UNSUPPORTED).  A call
+ *                         refused for its arguments leaves the mesh that was set; one that fails on the device
+ *                         (DSL_ERR_NOMEM, DSL_ERR_DEVICE) leaves the handle without a mesh.
+ * dsl_collide_pass      : query + response for every fluid particle.  Asynchronous.  Without a mesh: nothing.
+ * dsl_collider_query    : the four returns in host order, no response; any pointer may be NULL.  Blocking.
+ * While a mesh is set the step drivers run the collide pass after Update: dsl_wcsph_step after force + integrate,
+ * dsl_pcisph_step and DSL_PCI_END_STEP after Update (dsl_update_pass and dsl_force_pass stay one to one), the skin step
+ * is not taken, and dsl_stats.max_vel / max_f stay what Update saw.  Without a mesh no kernel is launched and no result
+ * changes by a bit. */
+int dsl_collider_set_mesh(dsl_handle *h, const float *vertices /* 9*T */, const float *normals /* 3*T */,
+                          size_t n_triangles, float radius, float restitution);
+int dsl_collide_pass(dsl_handle *h);
+int dsl_collider_query(dsl_handle *h, int32_t *tri /* N: index or -1 */, float *normal /* 3N */,
+                       float *coord /* 3N */, float *point /* 3N */);
 
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
@@ -489,8 +519,13 @@ enum {
   DSL_OPT_TILE_QUEUE = 26,        /* the two force kernels of a single domain draw their tiles from per-XCD counters as they go (a
                                      workgroup that drew cheap tiles takes more of them) instead of walking a share dealt in
                                      advance: 1 (default) from 8M particles on, 2 always, 0 never */
-  DSL_OPT_PCI_QINCR = 23          /* ... the rows kept from one correction iteration of a step to the next: only a query that
+  DSL_OPT_PCI_QINCR = 23,         /* ... the rows kept from one correction iteration of a step to the next: only a query that
                                      has changed cells is moved (default 1; 0: every iteration fills the rows afresh) */
+  DSL_OPT_COLLIDER_TRIANGLES = 32, /* (get) triangles of the collider mesh; 0: none */
+  DSL_OPT_COLLIDE_HITS = 33,       /* (get, blocking) particles the last collide pass moved (counted by the kernel) */
+  DSL_OPT_COLLIDE_CULL = 34        /* (set/get, default 1) broad phase: a wave skips a triangle -- a chunk of 256 by its box -- that
+                                      none of its particles can reach (csrc/kernels_collide.hpp states when); 0: every pair is
+                                      tested.  Results are identical either way */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);

@@ -9,7 +9,9 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$root/variants"
 if [ "$rev" = WORK ]; then src="$root"; else
   src=$(mktemp -d); git -C "$root" archive "$rev" dieselfluid_amd/csrc include | tar -x -C "$src"; fi
+extra=()  # (the collider's translation unit, where the revision has one)
+[ -f "$src/dieselfluid_amd/csrc/collide.hip" ] && extra=("$src/dieselfluid_amd/csrc/collide.hip")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -std=c++17 \
-  "$@" -o "$root/variants/libdslsph_$name.so" "$src/dieselfluid_amd/csrc/dslsph.hip"
+  "$@" -o "$root/variants/libdslsph_$name.so" "$src/dieselfluid_amd/csrc/dslsph.hip" "${extra[@]}"
 [ "$rev" = WORK ] || rm -rf "$src"
 ls -la "$root/variants/libdslsph_$name.so"

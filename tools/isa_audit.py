@@ -17,13 +17,14 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def device_asm(extra_flags=()):
+def device_asm(extra_flags=(), source="dslsph.hip"):
+    """gfx950 device assembly of one translation unit of the library (csrc/dslsph.hip, or csrc/collide.hip)"""
     sys.path.insert(0, ROOT)
     from dieselfluid_amd import _lib
     flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-fPIC", "-shared", "-Wall")]
     out = os.path.join(tempfile.mkdtemp(prefix="dsl_isa_"), "dslsph.s")
     cmd = ["/opt/rocm/bin/hipcc"] + flags + list(extra_flags) + ["-S", "--cuda-device-only", "-o", out,
-                                                                os.path.join(ROOT, "dieselfluid_amd", "csrc", "dslsph.hip")]
+                                                                os.path.join(ROOT, "dieselfluid_amd", "csrc", source)]
     subprocess.run(cmd, check=True, capture_output=True)
     return open(out).read()
 

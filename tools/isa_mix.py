@@ -1,4 +1,5 @@
-"""Instruction mix of kernels in an assembly file written by tools/kernel_resources.py --asm:
+"""Instruction mix of kernels in an assembly file written by tools/kernel_resources.py --asm (of either translation
+unit: --source dslsph.hip, the default, or --source collide.hip):
   python tools/isa_mix.py /tmp/dsl_device.s SUBSTR [SUBSTR ...]
 prints, per kernel whose mangled name contains every SUBSTR, the instruction count and the memory / barrier ops."""
 import re

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Compile dslsph.hip for gfx950 (device side only) and print VGPR / SGPR / occupancy / LDS per
-kernel from -Rpass-analysis=kernel-resource-usage; optionally keep the assembly.
+"""Compile one translation unit of the library for gfx950 (device side only) and print VGPR / SGPR / occupancy / LDS
+per kernel from -Rpass-analysis=kernel-resource-usage; optionally keep the assembly.
 
-  python tools/kernel_resources.py [--filter SUBSTR] [--asm /tmp/dsl.s] [-D MACRO ...]
+  python tools/kernel_resources.py [--source collide.hip] [--filter SUBSTR] [--asm /tmp/dsl.s] [-D MACRO ...]
+
+--source: a file of dieselfluid_amd/csrc; dslsph.hip (the engine, the default) or collide.hip (the collider's kernels).
 """
 import argparse
 import os
@@ -24,6 +26,7 @@ def demangle(names):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--source", default="dslsph.hip")
     ap.add_argument("--filter", default="")
     ap.add_argument("--asm", default="/tmp/dsl_device.s")
     ap.add_argument("-D", action="append", default=[])
@@ -32,7 +35,7 @@ def main():
     from dieselfluid_amd import _lib
     flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
     cmd = ["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-o", a.asm,
-                                            os.path.join(ROOT, "dieselfluid_amd", "csrc", "dslsph.hip"),
+                                            os.path.join(ROOT, "dieselfluid_amd", "csrc", a.source),
                                             "-Rpass-analysis=kernel-resource-usage"] + ["-D" + d for d in a.D]
     r = subprocess.run(cmd, text=True, capture_output=True)
     if r.returncode:
