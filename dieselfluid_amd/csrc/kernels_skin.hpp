@@ -519,7 +519,6 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
     have = feed.pop(di);
     int table_word = 0;
     if (have) table_word = tile_meta_request(desc, di);
-    const float ox = __int_as_float(m.centre[0]), oy = __int_as_float(m.centre[1]), oz = __int_as_float(m.centre[2]);
     const int ntarg = m.tprefix[kTB * kTB];
     const bool staged = m.overflow == 0;
     const unsigned int pad = pad_entry(m);
@@ -538,22 +537,7 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
       q0 = load_chunk(lists, tt0.g);
       q1 = load_chunk(lists, (size_t)lstride + tt0.g);
     }
-    if (staged)
-      stage_tile<3>(
-          m,
-          [&](int gg, float4* o) {
-            o[0] = load4u(p.x + gg);
-            o[1] = load4u(p.y + gg);
-            o[2] = load4u(p.z + gg);
-          },
-          [&](int slot, const float* o, bool real) {
-            float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-            if (real) {
-              const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-              v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-            }
-            A[slot] = v;
-          });
+    if (staged) stage_tile<3>(m, LoadPos4{p}, StoreTileRecord(A, m, c.inv_hh));
     if (have) tile_meta_store(metas[cur ^ 1], table_word);
     sync_lds();
     for_each_target<true, kLBlock>(ntarg, tid, tperm, [&](auto shared_c, int t, int sub, int k) {

@@ -108,13 +108,16 @@ __device__ __forceinline__ int tile_of_list_thread(const TileGrid& tg, int t) {
 
 #ifdef DSL_DIAG_STAMPS  // diagnostic build only: per-phase clocks of wave 0 of every block (s_memtime)
 __device__ unsigned long long g_diag[32];
-#define DSL_STAMP(var) const unsigned long long var = clock64()
-#define DSL_STAMP_ADD(slot, a, b) \
-  if (threadIdx.x == 0) atomicAdd(&g_diag[slot], (unsigned long long)((b) - (a)))
+// (the _IF forms: shared code stamps for the kernel that asks for it, `on` being a compile-time constant)
+#define DSL_STAMP_IF(on, var) const unsigned long long var = (on) ? clock64() : 0ull
+#define DSL_STAMP_ADD_IF(on, slot, a, b) \
+  if ((on) && threadIdx.x == 0) atomicAdd(&g_diag[slot], (unsigned long long)((b) - (a)))
 #else
-#define DSL_STAMP(var)
-#define DSL_STAMP_ADD(slot, a, b)
+#define DSL_STAMP_IF(on, var)
+#define DSL_STAMP_ADD_IF(on, slot, a, b)
 #endif
+#define DSL_STAMP(var) DSL_STAMP_IF(true, var)
+#define DSL_STAMP_ADD(slot, a, b) DSL_STAMP_ADD_IF(true, slot, a, b)
 
 // ---------------------------------------------------------------------------------
 // non-empty tile list
@@ -435,6 +438,16 @@ __device__ __forceinline__ void tile_meta_store(TileMeta& m, int word) {
   if (tid < kMetaInts) reinterpret_cast<int*>(&m)[tid] = word;
 }
 
+// largest interior row ir with prefix[ir] <= t: binary search over the 16 rows (TileMeta::tprefix by target index,
+// TileMeta::pprefix by pair slot)
+__device__ __forceinline__ int tile_row_of(const int (&prefix)[kTB * kTB + 1], int t) {
+  int ir = 0;
+  ir += (t >= prefix[ir + 8]) ? 8 : 0;
+  ir += (t >= prefix[ir + 4]) ? 4 : 0;
+  ir += (t >= prefix[ir + 2]) ? 2 : 0;
+  ir += (t >= prefix[ir + 1]) ? 1 : 0;
+  return ir;
+}
 // target index inside the tile -> its staged row, global slot, LDS record and tile-local x cell (1..4): the cell is
 // read off the row's cell table, i.e. exactly the cell the sort put the particle in (no second evaluation of the
 // cell rule, no load of the position)
@@ -442,7 +455,9 @@ struct TileTarget {
   int srow, g, own, lx;
 };
 __device__ __forceinline__ TileTarget tile_target(const TileMeta& m, int t) {
-  int ir = 0;  // largest interior row with tprefix[ir] <= t: binary search over the 16 rows
+  // (tile_row_of(m.tprefix, t), kept as its own copy: through the function the compiler forms srow below differently,
+  // and the bodies of the 35 force kernels and of k_list_build move -- two or three integer instructions each)
+  int ir = 0;
   ir += (t >= m.tprefix[ir + 8]) ? 8 : 0;
   ir += (t >= m.tprefix[ir + 4]) ? 4 : 0;
   ir += (t >= m.tprefix[ir + 2]) ? 2 : 0;
@@ -780,6 +795,286 @@ __device__ __forceinline__ void for_each_target(int ntarg, int tid, int tperm, B
 }
 
 // ---------------------------------------------------------------------------------
+// Parts the tiled sweeps share ("Shared parts of the tiled kernels")
+// ---------------------------------------------------------------------------------
+// (Pointer parameters are plain on purpose: `__restrict__` on a function inlined into several kernels adds alias scopes at
+// every call and moves the callers' code -- profiles/HISTORY.md, "Tiled kernels: shared parts written once".)
+// the positions as a staging source (stage_issue / stage_commit): the quad at slot g, one record
+struct LoadPos4 {
+  CSoa3 p;
+  __device__ __forceinline__ void operator()(int g, float4* o) const {
+    o[0] = load4u(p.x + g);
+    o[1] = load4u(p.y + g);
+    o[2] = load4u(p.z + g);
+  }
+};
+struct LoadPos1 {
+  CSoa3 p;
+  __device__ __forceinline__ void operator()(int g, float* o) const {
+    o[0] = p.x[g];
+    o[1] = p.y[g];
+    o[2] = p.z[g];
+  }
+};
+
+// A staged position as the FAST sweeps read it: x, y, z relative to the tile centre and w = -|x|^2/h^2 (see "D (tiled)"
+// below for the arithmetic this buys).
+__device__ __forceinline__ float4 tile_record(const float* o, bool real, float ox, float oy, float oz, float inv_hh) {
+  float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
+  if (real) {
+    const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
+    v = make_float4(x, y, z, -inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
+  }
+  return v;
+}
+// stage_commit's `store` for an image that holds nothing else
+struct StoreTileRecord {
+  float4* img;
+  float ox, oy, oz, inv_hh;
+  __device__ __forceinline__ StoreTileRecord(float4* image, const TileMeta& m, float inv_hh_)
+      : img(image), ox(__int_as_float(m.centre[0])), oy(__int_as_float(m.centre[1])), oz(__int_as_float(m.centre[2])), inv_hh(inv_hh_) {}
+  __device__ __forceinline__ void operator()(int slot, const float* o, bool real) const { img[slot] = tile_record(o, real, ox, oy, oz, inv_hh); }
+};
+
+// The nine x-runs around staged row srow, z-plane by z-plane: f(ri, rr), ri = 0..8 the run, rr its staged row.  Plain: the
+// lane takes all nine; SHARED (for_each_target): lane `sub` of a group of k takes every k-th.
+template <bool SHARED, class F>
+__device__ __forceinline__ void for_each_run(int srow, int sub, int k, F&& f) {
+  if constexpr (!SHARED) {
+    int ri = 0;
+#pragma unroll 1
+    for (int dz = -kTH; dz <= kTH; dz += kTH) {
+#pragma unroll 1
+      for (int dy = -1; dy <= 1; ++dy, ++ri) f(ri, srow + dz + dy);
+    }
+  } else {
+#pragma unroll 1
+    for (int ri = sub; ri < 9; ri += k) f(ri, srow + (ri / 3 - 1) * kTH + (ri % 3 - 1));
+  }
+}
+
+// FAST density of the particle in slot g from global memory, the grid's 27 cells: what a target of a tile beyond the LDS
+// budget gets (already scaled by m A, the particle itself left out)
+__device__ __forceinline__ float density_global_fast(const DevConsts& c, const int* cell_start, const CSoa3& p, int g) {
+  const float xi = p.x[g], yi = p.y[g], zi = p.z[g];
+  float acc = 0.0f;
+  for_each_grid_candidate(c, cell_start, xi, yi, zi, [&](int j) {
+    if (j == g) return;
+    const float dx = xi - p.x[j], dy = yi - p.y[j], dz = zi - p.z[j];
+    const float r2 = dist2<true>(dx, dy, dz);
+    if (r2 < c.hh) {
+      const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
+      acc = __builtin_fmaf(c.mass * c.A, q * q, acc);
+    }
+  });
+  return acc;
+}
+// FAST: rho and P/rho^2 of the particle in slot g, acc its density
+__device__ __forceinline__ void store_density_fast(const DevConsts& c, const Bnd& bnd, float* rho, float* pterm, int g, float acc) {
+  if (bnd.is(g)) {  // a boundary particle reads as density 0, P/rho^2 = 0/0 (Bnd, sph_device.hpp)
+    rho[g] = 0.0f;
+    pterm[g] = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  rho[g] = acc;
+  // An isolated particle (rho = 0) has no neighbour for which the reference would ever form
+  // P/rho^2 (sph_field.go:183-199 only does so inside the j != i loop); the masked sweeps do
+  // visit the particle itself, so its own term has to be a harmless 0 rather than 0/0.
+  const float pr = tait_eos<true>(c, acc, c.eos_d0_grad);
+  pterm[g] = acc > 0.0f ? dsl_div<true>(pr, acc * acc) : 0.0f;
+}
+
+// SPHField.DensityF (sph_field.go:137-152), FAST, at a query point (rx, ry, rz) relative to the centre of the staged
+// tile (table m, image A): the sum of q^2 over the nine runs around staged row qrow, tile-local x cell lx, with
+// q = clamp(1 - r^2/h^2) = clamp(a0 + w_j + (2/h^2) q.x_j) as in k_density_tiled; the caller scales and adds W0.
+__device__ __forceinline__ float densityf_tile_sum(const TileMeta& m, const float4* __restrict__ A, float inv_hh, float rx, float ry,
+                                                   float rz, int qrow, int lx) {
+  const float two_hh = 2.0f * inv_hh;
+  const float sx = two_hh * rx, sy = two_hh * ry, sz = two_hh * rz;
+  const float a0 = 1.0f - inv_hh * __builtin_fmaf(rz, rz, __builtin_fmaf(ry, ry, rx * rx));
+  float acc = 0.f, acc1 = 0.f;
+  auto test4 = [&](int jj) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float4 cnd = A[jj + u];
+      const float q = fma_clamp01(cnd.z, sz, __builtin_fmaf(cnd.y, sy, __builtin_fmaf(cnd.x, sx, cnd.w + a0)));
+      if (u & 1) acc1 = __builtin_fmaf(q, q, acc1);
+      else acc = __builtin_fmaf(q, q, acc);
+    }
+  };
+  for_each_run<false>(qrow, 0, 1, [&](int, int rr) {
+    int j, je;
+    tile_run(m, rr, lx, j, je);
+    for (; j + 4 < je; j += 8) {
+      test4(j);
+      test4(j + 4);
+    }
+    if (j < je) test4(j);
+  });
+  return acc + acc1;
+}
+// the same from global memory, the grid's 27 cells around the query: starts at W0, self included
+__device__ __forceinline__ float densityf_global(const DevConsts& c, const int* cell_start, const CSoa3& p, float qx,
+                                                 float qy, float qz) {
+  float density = c.W0;
+  for_each_grid_candidate(c, cell_start, qx, qy, qz, [&](int j) {
+    const float dx = qx - p.x[j], dy = qy - p.y[j], dz = qz - p.z[j];
+    const float r2 = dist2<true>(dx, dy, dz);
+    if (r2 < c.hh) {
+      const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
+      density = __builtin_fmaf(c.mass * c.A, q * q, density);
+    }
+  });
+  return density;
+}
+// pressure accumulate + the iteration's error (pcisph_darwin.go:76-92); ebits: the lane's running maximum
+__device__ __forceinline__ void pci_accumulate(const DevConsts& c, float* press, int g, float density, unsigned int& ebits) {
+  const float density_error = density - c.ref_density;
+  const float abs_err = density_error * __builtin_amdgcn_rcpf(c.ref_density);
+  press[g] += density_error * c.delta;
+  const unsigned int eb = nonneg_bits(abs_err);
+  ebits = eb > ebits ? eb : ebits;
+}
+
+// The tile loop with a DOUBLE-BUFFERED LDS image (r03; k_density_tiled's FAST form, k_pci_density_tiled,
+// k_pci_density_qtiled).  A tile's life used to be barrier, staging (load issue, one exposed
+// memory round trip, LDS writes), barrier, sweep: per-phase clocks put the sweep at 57 % of it, and with two
+// workgroups per CU a quarter of the time NEITHER was sweeping (profiles/r03_*).  Now the loads of tile k+1 are
+// issued right behind the barrier that starts the sweep of tile k (12 registers per lane carry them through it),
+// every wave commits them to the OTHER image as soon as ITS OWN sweep is over -- no barrier in between: that image
+// was last read by the sweep of tile k-1, which every wave had left before this tile's barrier -- and the table of
+// tile k+2 rotates through a third copy the same way.  One barrier per tile, no exposed round trip.
+// metas: three tables, Abuf: two images; commit(table, registers, image): registers -> records; sweep(table, image).
+// STAMPS: the per-phase clocks of a DSL_DIAG_STAMPS build (k_density_tiled's).
+template <bool STAMPS, class Commit, class Sweep>
+__device__ __forceinline__ void sweep_tiles_double_buffered(TileFeed& feed, const int* desc, TileMeta* metas,
+                                                            float4 (*Abuf)[kTCap], const LoadPos4& load4, Commit&& commit,
+                                                            Sweep&& sweep) {
+  int di = 0;
+  bool have = feed.pop(di);
+  if (!have) return;
+  tile_meta_store(metas[0], tile_meta_request(desc, di));
+  bool have_next = feed.pop(di);
+  int table_word = have_next ? tile_meta_request(desc, di) : 0;
+  sync_lds();  // the first tile's table is visible
+  {                 // the first tile is staged in the open: nothing to hide it under yet
+    StageRegs<3> sr;
+    if (!metas[0].overflow) {
+      stage_issue<3>(metas[0], load4, sr);
+      commit(metas[0], sr, Abuf[0]);
+    }
+  }
+  if (have_next) tile_meta_store(metas[1], table_word);
+  int mc = 0, mn = 1, mnn = 2;  // tables of this tile, the next one, the one after
+  for (int cur = 0; have; cur ^= 1) {
+    DSL_STAMP_IF(STAMPS, d0);
+    sync_lds();  // image `cur` is complete, the next tile's table visible, image `cur ^ 1` and table `mnn` free
+    DSL_STAMP_IF(STAMPS, d1);
+    DSL_STAMP_ADD_IF(STAMPS, 4, d0, d1);
+    StageRegs<3> sr;
+    bool have_nn = false, stage_next = false;
+    table_word = 0;
+    if (have_next) {
+      stage_next = metas[mn].overflow == 0;
+      if (stage_next) stage_issue<3>(metas[mn], load4, sr);
+      have_nn = feed.pop(di);
+      if (have_nn) table_word = tile_meta_request(desc, di);
+    }
+    DSL_STAMP_IF(STAMPS, d1b);
+    DSL_STAMP_ADD_IF(STAMPS, 12, d1, d1b);  // next tile: load issue
+    sweep(metas[mc], Abuf[cur]);
+    DSL_STAMP_IF(STAMPS, d4);
+    if (stage_next) commit(metas[mn], sr, Abuf[cur ^ 1]);
+    if (have_nn) tile_meta_store(metas[mnn], table_word);
+    DSL_STAMP_IF(STAMPS, d5);
+    DSL_STAMP_ADD_IF(STAMPS, 13, d4, d5);  // next tile: wait for its data (if it has not landed under the sweep) + LDS writes
+    have = have_next;
+    have_next = have_nn;
+    const int t = mc;
+    mc = mn;
+    mn = mnn;
+    mnn = t;
+  }
+}
+
+// The tile loop of the 256-thread pair kernels (k_density_pair, k_pci_density_qpair; kPBlock, below): one image, two
+// tables, the next tile's table requested ahead of the staging loads.  A tile that fits is staged as tile_records into A;
+// then body(table, overflow) sweeps it -- or, for a tile beyond the LDS budget, does without the image.
+template <int BLOCK, class Body>
+__device__ __forceinline__ void sweep_tiles_pair(const DevConsts& c, TileFeed& feed, const int* desc, TileMeta* metas,
+                                                 float4* A, const CSoa3& p, Body&& body) {
+  const int tid = threadIdx.x;
+  const LoadPos4 load4{p};
+  const LoadPos1 load1{p};
+  // a tile's table: kMetaInts dwords, two per lane
+  auto meta_request = [&](int desc_index, int (&w)[2]) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int i = tid + k * BLOCK;
+      w[k] = i < kMetaInts ? desc[(size_t)desc_index * kMetaInts + i] : 0;
+    }
+  };
+  auto meta_store = [&](TileMeta& m, const int (&w)[2]) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int i = tid + k * BLOCK;
+      if (i < kMetaInts) reinterpret_cast<int*>(&m)[i] = w[k];
+    }
+  };
+  int di = 0;
+  bool have = feed.pop(di);
+  if (!have) return;
+  {
+    int w[2];
+    meta_request(di, w);
+    meta_store(metas[0], w);
+  }
+  for (int cur = 0; have; cur ^= 1) {
+    TileMeta& m = metas[cur];
+    sync_lds();  // the previous tile's sweep is over: its LDS records are free, this tile's table is visible
+    have = feed.pop(di);
+    int tw[2] = {0, 0};
+    if (have) meta_request(di, tw);
+    const bool ovf = m.overflow != 0;
+    if (!ovf) {
+      const StoreTileRecord store(A, m, c.inv_hh);
+      // 36 rows x 14 quads = 504 quad slots on 256 lanes: two per lane, all six loads in flight together
+      StageRegs<3> sr0, sr1;
+      stage_issue<3>(m, load4, sr0, tid);
+      stage_issue<3>(m, load4, sr1, tid + BLOCK);
+      stage_commit<3>(m, sr0, load1, store, tid);
+      stage_commit<3>(m, sr1, load1, store, tid + BLOCK);
+    }
+    if (have) meta_store(metas[cur ^ 1], tw);
+    sync_lds();
+    body(m, ovf);
+  }
+}
+// EXACT walks: the set bits of up to three mask words, a word's earliest candidate (its highest bit) first; top: the
+// record of a word's bit 0.  Empty words to the back, one shift per exhausted word.
+struct MaskQueue {
+  unsigned int mm, n1, n2;
+  int top, tp1, tp2;
+  __device__ __forceinline__ void shift() {
+    mm = n1;
+    top = tp1;
+    n1 = n2;
+    tp1 = tp2;
+    n2 = 0u;
+  }
+  // the next candidate's record (pad_rec once the queue is empty); counts: there was one and it is not `own`
+  __device__ __forceinline__ int take(int own, int pad_rec, bool& counts) {
+    const bool has = mm != 0u;
+    const int b = 31 - __builtin_clz(mm | 1u);  // highest set bit = earliest candidate
+    const int idx = has ? top - b : pad_rec;
+    mm = has ? (mm & ~(1u << b)) : 0u;
+    counts = has && idx != own;  // `if i != pIndex` (sph_field.go:164)
+    if (mm == 0u) shift();
+    return idx;
+  }
+};
+
+// ---------------------------------------------------------------------------------
 // D (tiled): densities + P/rho^2
 //
 // Candidate coordinates are staged RELATIVE TO THE TILE CENTRE together with w = -|x|^2/h^2, so
@@ -807,13 +1102,7 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
                                                           const int* __restrict__ cell_start, Bnd bnd, CSoa3 p,
                                                           float* __restrict__ rho, float* __restrict__ pterm,
                                                           unsigned int* __restrict__ nmask, int mstride) {
-  // FAST: the LDS image is DOUBLE-BUFFERED (r03).  A tile's life used to be barrier, staging (load issue, one exposed
-  // memory round trip, LDS writes), barrier, sweep: per-phase clocks put the sweep at 57 % of it, and with two
-  // workgroups per CU a quarter of the time NEITHER was sweeping (profiles/r03_*).  Now the loads of tile k+1 are
-  // issued right behind the barrier that starts the sweep of tile k (12 registers per lane carry them through it),
-  // every wave commits them to the OTHER image as soon as ITS OWN sweep is over -- no barrier in between: that image
-  // was last read by the sweep of tile k-1, which every wave had left before this tile's barrier -- and the table of
-  // tile k+2 rotates through a third copy the same way.  One barrier per tile, no exposed round trip.
+  // FAST: the LDS image is double-buffered (sweep_tiles_double_buffered has the why).
   // 2 x 36.9 KB + 3 tables = 78 KB per workgroup: two workgroups still fit a CU's 160 KB.
   // EXACT keeps one image (its second array holds the pre-filter's tile-relative records) and the old order.
 #ifdef DSL_DENSITY_SINGLE_BUFFER  // (A/B and diagnostic builds)
@@ -831,16 +1120,8 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
   // (n_tiles is the base of the tile-list counters here; a slab always has half-empty ghost tiles: the host
   // launches the pass-sharing instantiation alone)
   if (!EXACT && c.slab_axis < 0 && share_wanted(n_tiles) != SHARE) return;
-  auto load4 = [&](int g, float4* o) {
-    o[0] = load4u(p.x + g);
-    o[1] = load4u(p.y + g);
-    o[2] = load4u(p.z + g);
-  };
-  auto load1 = [&](int g, float* o) {
-    o[0] = p.x[g];
-    o[1] = p.y[g];
-    o[2] = p.z[g];
-  };
+  const LoadPos4 load4{p};
+  const LoadPos1 load1{p};
   // EXACT: the walk divides with exact_div (sph_device.hpp), which equals `/` bit for bit while every staged
   // coordinate is 0 or between 2^-20 and 2^20 in magnitude; a tile with any other value takes the global sweep
   // (checked on the staging registers, stage_values_ok; rows longer than 56 records are not exempt: their tail is
@@ -849,11 +1130,7 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
   auto commit = [&](const TileMeta& mt, const StageRegs<3>& sr, float4* img) {
     const float ox = __int_as_float(mt.centre[0]), oy = __int_as_float(mt.centre[1]), oz = __int_as_float(mt.centre[2]);
     stage_commit<3>(mt, sr, load1, [&](int slot, const float* o, bool real) {
-      float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-      if (real) {
-        const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-        v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-      }
+      const float4 v = tile_record(o, real, ox, oy, oz, c.inv_hh);
       if constexpr (EXACT) {  // raw coordinates; a pad is far away from everything
         img[slot] = real ? make_float4(o[0], o[1], o[2], 0.0f) : make_float4(kFar, kFar, kFar, 0.0f);
         R[slot] = v;
@@ -914,6 +1191,48 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
             const float mw = c.mass * w;
             density = density + mw;
           };
+          // the mask word of the candidates [j, jend), at most 32 of them, first candidate in the highest bit
+          auto candidate_mask = [&](int j, int jend) {
+            unsigned int mask = 0u;
+            if (prefilter) {
+              for (int jj = j; jj < jend; jj += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                  const float4 cnd = R[jj + u];
+                  const float t = __builtin_fmaf(cnd.z, qsz, __builtin_fmaf(cnd.y, qsy, __builtin_fmaf(cnd.x, qsx, cnd.w + qa0)));
+                  mask_push_lt(mask, -1.0e-3f, t);
+                }
+              }
+            } else {
+              for (int jj = j; jj < jend; jj += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                  const float4 cnd = A[jj + u];
+                  const float dx = me.x - cnd.x, dy = me.y - cnd.y, dz = me.z - cnd.z;
+                  mask_push_lt(mask, dist2<false>(dx, dy, dz), c.r2_thr);
+                }
+              }
+            }
+            // the sweep tests whole groups of 4: the up to 3 records behind the run belong to a cell the
+            // reference's stencil does not visit (or are pads); their bits, the lowest, are dropped
+            return mask & (~0u << ((4 - ((jend - j) & 3)) & 3));
+          };
+          // two candidates per trip, the next trip's record requested before the arithmetic
+          auto walk = [&](MaskQueue& q) {
+            if (__builtin_amdgcn_ballot_w64(q.mm != 0u) != 0ull) {
+              bool cp, cq;
+              float4 pr = A[q.take(own, pad_rec, cp)];
+              bool more;
+              do {
+                const float4 qr = A[q.take(own, pad_rec, cq)];
+                add(pr, cp);
+                more = __builtin_amdgcn_ballot_w64(q.mm != 0u) != 0ull;
+                const bool cq2 = cq;
+                pr = A[q.take(own, pad_rec, cp)];
+                add(qr, cq2);
+              } while (more);
+            }
+          };
           auto run_by_run = [&](int ri) {
             const int rr = srow + (ri / 3 - 1) * kTH + (ri % 3 - 1);
             int j, je;
@@ -922,55 +1241,11 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
             // chunks of up to 32 candidates: sweep -> mask word -> walk of its set bits, first candidate first
             for (int chunk = 0; j < je; ++chunk, j += 32) {
               const int jend = min(je, j + 32);
-              unsigned int mask = 0u;
-              if (prefilter) {
-                for (int jj = j; jj < jend; jj += 4) {
-#pragma unroll
-                  for (int u = 0; u < 4; ++u) {
-                    const float4 cnd = R[jj + u];
-                    const float t = __builtin_fmaf(cnd.z, qsz, __builtin_fmaf(cnd.y, qsy, __builtin_fmaf(cnd.x, qsx, cnd.w + qa0)));
-                    mask_push_lt(mask, -1.0e-3f, t);
-                  }
-                }
-              } else {
-                for (int jj = j; jj < jend; jj += 4) {
-#pragma unroll
-                  for (int u = 0; u < 4; ++u) {
-                    const float4 cnd = A[jj + u];
-                    const float dx = me.x - cnd.x, dy = me.y - cnd.y, dz = me.z - cnd.z;
-                    mask_push_lt(mask, dist2<false>(dx, dy, dz), c.r2_thr);
-                  }
-                }
-              }
-              // the sweep tests whole groups of 4: the up to 3 records behind the run belong to a cell the
-              // reference's stencil does not visit (or are pads); their bits, the lowest, are dropped
-              mask &= ~0u << ((4 - ((jend - j) & 3)) & 3);
+              const unsigned int mask = candidate_mask(j, jend);
               if (chunk == 0) nmask[(size_t)ri * mstride + g] = mask;
               else if (chunk == 1) nmask[(size_t)(kMaskHigh + ri) * mstride + g] = mask;
-              const int top = j + ((jend - j + 3) & ~3) - 1;  // record of bit 0
-              unsigned int mm = mask;
-              auto take = [&](bool& counts) {
-                const bool has = mm != 0u;
-                const int b = 31 - __builtin_clz(mm | 1u);  // highest set bit = earliest candidate
-                const int idx = has ? top - b : pad_rec;
-                mm &= ~(1u << b);
-                mm = has ? mm : 0u;
-                counts = has && idx != own;  // `if i != pIndex` (sph_field.go:164)
-                return idx;
-              };
-              if (__builtin_amdgcn_ballot_w64(mm != 0u) != 0ull) {
-                bool cp, cq;
-                float4 pr = A[take(cp)];
-                bool more;
-                do {  // two candidates per trip, the next trip's record requested before the arithmetic
-                  const float4 qr = A[take(cq)];
-                  add(pr, cp);
-                  more = __builtin_amdgcn_ballot_w64(mm != 0u) != 0ull;
-                  const bool cq2 = cq;
-                  pr = A[take(cp)];
-                  add(qr, cq2);
-                } while (more);
-              }
+              MaskQueue q{mask, 0u, 0u, j + ((jend - j + 3) & ~3) - 1, 0, 0};  // (top: the record of bit 0)
+              walk(q);
             }
           };
           // Three runs per walk (the z-plane's, as in the force kernel): the candidate sweeps of the three runs first -- their
@@ -998,74 +1273,19 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
               const int ri = 3 * g3 + u, j = jj[u], jend = jje[u];
-              unsigned int mask = 0u;
-              if (prefilter) {
-                for (int q4 = j; q4 < jend; q4 += 4) {
-#pragma unroll
-                  for (int v = 0; v < 4; ++v) {
-                    const float4 cnd = R[q4 + v];
-                    const float t = __builtin_fmaf(cnd.z, qsz, __builtin_fmaf(cnd.y, qsy, __builtin_fmaf(cnd.x, qsx, cnd.w + qa0)));
-                    mask_push_lt(mask, -1.0e-3f, t);
-                  }
-                }
-              } else {
-                for (int q4 = j; q4 < jend; q4 += 4) {
-#pragma unroll
-                  for (int v = 0; v < 4; ++v) {
-                    const float4 cnd = A[q4 + v];
-                    const float dx = me.x - cnd.x, dy = me.y - cnd.y, dz = me.z - cnd.z;
-                    mask_push_lt(mask, dist2<false>(dx, dy, dz), c.r2_thr);
-                  }
-                }
-              }
-              mask &= ~0u << ((4 - ((jend - j) & 3)) & 3);
+              const unsigned int mask = candidate_mask(j, jend);
               nmask[(size_t)ri * mstride + g] = mask;
               mk[u] = mask;
               tp[u] = j + ((jend - j + 3) & ~3) - 1;  // record of bit 0
             }
-            // the queue: empty words to the back, one shift per exhausted word
-            unsigned int mm = mk[0], n1 = mk[1], n2 = mk[2];
-            int top = tp[0], tp1 = tp[1], tp2 = tp[2];
-            if (n1 == 0u) {
-              n1 = n2;
-              tp1 = tp2;
-              n2 = 0u;
+            MaskQueue q{mk[0], mk[1], mk[2], tp[0], tp[1], tp[2]};
+            if (q.n1 == 0u) {  // empty words to the back
+              q.n1 = q.n2;
+              q.tp1 = q.tp2;
+              q.n2 = 0u;
             }
-            if (mm == 0u) {
-              mm = n1;
-              top = tp1;
-              n1 = n2;
-              tp1 = tp2;
-              n2 = 0u;
-            }
-            auto take = [&](bool& counts) {
-              const bool has = mm != 0u;
-              const int b = 31 - __builtin_clz(mm | 1u);  // highest set bit = earliest candidate
-              const int idx = has ? top - b : pad_rec;
-              mm = has ? (mm & ~(1u << b)) : 0u;
-              counts = has && idx != own;  // `if i != pIndex` (sph_field.go:164)
-              if (mm == 0u) {
-                mm = n1;
-                top = tp1;
-                n1 = n2;
-                tp1 = tp2;
-                n2 = 0u;
-              }
-              return idx;
-            };
-            if (__builtin_amdgcn_ballot_w64(mm != 0u) != 0ull) {
-              bool cp, cq;
-              float4 pr = A[take(cp)];
-              bool more;
-              do {
-                const float4 qr = A[take(cq)];
-                add(pr, cp);
-                more = __builtin_amdgcn_ballot_w64(mm != 0u) != 0ull;
-                const bool cq2 = cq;
-                pr = A[take(cp)];
-                add(qr, cq2);
-              } while (more);
-            }
+            if (q.mm == 0u) q.shift();
+            walk(q);
           }
           acc = density;
         } else if (sub == 0) {
@@ -1136,29 +1356,10 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
             nmask[(size_t)(kMaskHigh + ri) * mstride + g] = mask;
           }
         };
-        if constexpr (!SHARED) {
-          int ri = 0;
-#pragma unroll 1
-          for (int dz = -kTH; dz <= kTH; dz += kTH) {
-#pragma unroll 1
-            for (int dy = -1; dy <= 1; ++dy, ++ri) sweep_run(ri, srow + dz + dy);
-          }
-        } else {
-#pragma unroll 1
-          for (int ri = sub; ri < 9; ri += k) sweep_run(ri, srow + (ri / 3 - 1) * kTH + (ri % 3 - 1));
-        }
+        for_each_run<SHARED>(srow, sub, k, sweep_run);
         acc += acc1;
       } else if (sub == 0) {
-        const float xi = p.x[g], yi = p.y[g], zi = p.z[g];
-        for_each_grid_candidate(c, cell_start, xi, yi, zi, [&](int j) {
-          if (j == g) return;
-          const float dx = xi - p.x[j], dy = yi - p.y[j], dz = zi - p.z[j];
-          const float r2 = dist2<true>(dx, dy, dz);
-          if (r2 < c.hh) {
-            const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-            acc = __builtin_fmaf(c.mass * c.A, q * q, acc);
-          }
-        });
+        acc = density_global_fast(c, cell_start, p, g);
       }
       if constexpr (SHARED) {
         for (int o = 1; o < k; o <<= 1) {  // the lanes of a group are active together
@@ -1167,69 +1368,20 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
         if (sub != 0) return;
       }
       if (!ovf) acc = (acc - self_term) * (c.mass * c.A);  // the particle met itself once (q = 1)
-      if (bnd.is(g)) {  // a boundary particle reads as density 0, P/rho^2 = 0/0 (Bnd, sph_device.hpp)
-        rho[g] = 0.0f;
-        pterm[g] = __uint_as_float(0x7fc00000u);
-        return;
-      }
-      rho[g] = acc;
-      // An isolated particle (rho = 0) has no neighbour for which the reference would ever form
-      // P/rho^2 (sph_field.go:183-199 only does so inside the j != i loop); the masked sweeps do
-      // visit the particle itself, so its own term has to be a harmless 0 rather than 0/0.
-      const float pr = tait_eos<true>(c, acc, c.eos_d0_grad);
-      pterm[g] = acc > 0.0f ? dsl_div<true>(pr, acc * acc) : 0.0f;
+      store_density_fast(c, bnd, rho, pterm, g, acc);
     });
     DSL_STAMP(d3);
     DSL_STAMP_ADD(6, d2, d3);
   };
   TileFeed feed(desc_of, *n_tiles);
-  int di = 0;
-  bool have = feed.pop(di);
-  if (!have) return;
-  tile_meta_store(metas[0], tile_meta_request(desc, di));
   if constexpr (DB) {
-    bool have_next = feed.pop(di);
-    int table_word = have_next ? tile_meta_request(desc, di) : 0;
-    sync_lds();  // the first tile's table is visible
-    {                 // the first tile is staged in the open: nothing to hide it under yet
-      StageRegs<3> sr;
-      if (!metas[0].overflow) {
-        stage_issue<3>(metas[0], load4, sr);
-        commit(metas[0], sr, Abuf[0]);
-      }
-    }
-    if (have_next) tile_meta_store(metas[1], table_word);
-    int mc = 0, mn = 1, mnn = 2;  // tables of this tile, the next one, the one after
-    for (int cur = 0; have; cur ^= 1) {
-      DSL_STAMP(d0);
-      sync_lds();  // image `cur` is complete, the next tile's table visible, image `cur ^ 1` and table `mnn` free
-      DSL_STAMP(d1);
-      DSL_STAMP_ADD(4, d0, d1);
-      StageRegs<3> sr;
-      bool have_nn = false, stage_next = false;
-      table_word = 0;
-      if (have_next) {
-        stage_next = metas[mn].overflow == 0;
-        if (stage_next) stage_issue<3>(metas[mn], load4, sr);
-        have_nn = feed.pop(di);
-        if (have_nn) table_word = tile_meta_request(desc, di);
-      }
-      DSL_STAMP(d1b);
-      DSL_STAMP_ADD(12, d1, d1b);  // next tile: load issue
-      sweep(metas[mc], Abuf[cur], false);
-      DSL_STAMP(d4);
-      if (stage_next) commit(metas[mn], sr, Abuf[cur ^ 1]);
-      if (have_nn) tile_meta_store(metas[mnn], table_word);
-      DSL_STAMP(d5);
-      DSL_STAMP_ADD(13, d4, d5);  // next tile: wait for its data (if it has not landed under the sweep) + LDS writes
-      have = have_next;
-      have_next = have_nn;
-      const int t = mc;
-      mc = mn;
-      mn = mnn;
-      mnn = t;
-    }
+    sweep_tiles_double_buffered<true>(feed, desc, metas, Abuf, load4, commit,
+                                      [&](const TileMeta& m, const float4* __restrict__ A) { sweep(m, A, false); });
   } else {
+    int di = 0;
+    bool have = feed.pop(di);
+    if (!have) return;
+    tile_meta_store(metas[0], tile_meta_request(desc, di));
     for (int cur = 0; have; cur ^= 1) {
       TileMeta& m = metas[cur];
       sync_lds();  // the previous tile's sweep is over: its LDS records are free, this tile's table is visible
@@ -1278,11 +1430,7 @@ struct PairSlot {
   bool two;              // the slot holds two targets (g + 1, own + 1 is the second)
 };
 __device__ __forceinline__ PairSlot pair_slot(const TileMeta& m, int u) {
-  int ir = 0;  // largest interior row with pprefix[ir] <= u
-  ir += (u >= m.pprefix[ir + 8]) ? 8 : 0;
-  ir += (u >= m.pprefix[ir + 4]) ? 4 : 0;
-  ir += (u >= m.pprefix[ir + 2]) ? 2 : 0;
-  ir += (u >= m.pprefix[ir + 1]) ? 1 : 0;
+  const int ir = tile_row_of(m.pprefix, u);
   const int4 w = m.trow[ir];
   const int b1 = m.tprefix[ir], b2 = w.z & 0xffff, b3 = (int)((unsigned)w.z >> 16), b4 = w.w, b5 = m.tprefix[ir + 1];
   const int n1 = (b2 - b1 + 1) >> 1, n2 = (b3 - b2 + 1) >> 1, n3 = (b4 - b3 + 1) >> 1;
@@ -1325,66 +1473,8 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
   // (WIDE: the skin step launches the pass-sharing instantiation alone -- its tiles of 4 x 4 x 3 wide cells hold a few
   // targets more or less than a block -- and saves a launch that would only find out it is not wanted)
   if (!WIDE && c.slab_axis < 0 && share_wanted(n_tiles) != SHARE) return;
-  auto load4 = [&](int g, float4* o) {
-    o[0] = load4u(p.x + g);
-    o[1] = load4u(p.y + g);
-    o[2] = load4u(p.z + g);
-  };
-  auto load1 = [&](int g, float* o) {
-    o[0] = p.x[g];
-    o[1] = p.y[g];
-    o[2] = p.z[g];
-  };
-  // a tile's table: kMetaInts dwords, two per lane
-  auto meta_request = [&](int desc_index, int (&w)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = tid + k * kPBlock;
-      w[k] = i < kMetaInts ? desc[(size_t)desc_index * kMetaInts + i] : 0;
-    }
-  };
-  auto meta_store = [&](TileMeta& m, const int (&w)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = tid + k * kPBlock;
-      if (i < kMetaInts) reinterpret_cast<int*>(&m)[i] = w[k];
-    }
-  };
   TileFeed feed(desc_of, *n_tiles);
-  int di = 0;
-  bool have = feed.pop(di);
-  if (!have) return;
-  {
-    int w[2];
-    meta_request(di, w);
-    meta_store(metas[0], w);
-  }
-  for (int cur = 0; have; cur ^= 1) {
-    TileMeta& m = metas[cur];
-    sync_lds();  // the previous tile's sweep is over: its LDS records are free, this tile's table is visible
-    have = feed.pop(di);
-    int tw[2] = {0, 0};
-    if (have) meta_request(di, tw);
-    const bool ovf = m.overflow != 0;
-    if (!ovf) {
-      const float ox = __int_as_float(m.centre[0]), oy = __int_as_float(m.centre[1]), oz = __int_as_float(m.centre[2]);
-      auto store = [&](int slot, const float* o, bool real) {
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-        if (real) {
-          const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-          v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-        }
-        A[slot] = v;
-      };
-      // 36 rows x 14 quads = 504 quad slots on 256 lanes: two per lane, all six loads in flight together
-      StageRegs<3> sr0, sr1;
-      stage_issue<3>(m, load4, sr0, tid);
-      stage_issue<3>(m, load4, sr1, tid + kPBlock);
-      stage_commit<3>(m, sr0, load1, store, tid);
-      stage_commit<3>(m, sr1, load1, store, tid + kPBlock);
-    }
-    if (have) meta_store(metas[cur ^ 1], tw);
-    sync_lds();
+  sweep_tiles_pair<kPBlock>(c, feed, desc, metas, A, p, [&](const TileMeta& m, bool ovf) {
     if (ovf) {
       // A tile beyond the LDS budget: its targets one per lane, by the target prefix alone, the grid's 27 cells from
       // global memory.  (Not by pair slots: a tile table packs its in-row cell boundaries into 16 bits -- TileMeta::trow
@@ -1393,28 +1483,11 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
         const int ntarg = m.tprefix[kTB * kTB];
         for (int t = tid; t < ntarg; t += kPBlock) {
           const int g = tile_target(m, t).g;
-          if (bnd.is(g)) {
-            rho[g] = 0.0f;
-            pterm[g] = __uint_as_float(0x7fc00000u);
-            continue;
-          }
-          const float xi = p.x[g], yi = p.y[g], zi = p.z[g];
-          float a = 0.0f;
-          for_each_grid_candidate(c, cell_start, xi, yi, zi, [&](int j) {
-            if (j == g) return;
-            const float dx = xi - p.x[j], dy = yi - p.y[j], dz = zi - p.z[j];
-            const float r2 = dist2<true>(dx, dy, dz);
-            if (r2 < c.hh) {
-              const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-              a = __builtin_fmaf(c.mass * c.A, q * q, a);
-            }
-          });
-          rho[g] = a;
-          const float pr = tait_eos<true>(c, a, c.eos_d0_grad);
-          pterm[g] = a > 0.0f ? dsl_div<true>(pr, a * a) : 0.0f;
+          const float a = bnd.is(g) ? 0.0f : density_global_fast(c, cell_start, p, g);  // (a boundary particle: no sweep)
+          store_density_fast(c, bnd, rho, pterm, g, a);
         }
       }
-      continue;
+      return;
     }
     const int nslots = m.pprefix[kTB * kTB];
     for_each_target<SHARE, kPBlock, kPairNine>(nslots, tid, tid, [&](auto shared_c, int u, int sub, int k) {
@@ -1423,99 +1496,69 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
       const int srow = ps.srow, lx = ps.lx, g0 = ps.g;
       const bool two = ps.two;
       float acc[2] = {0.0f, 0.0f}, accb[2] = {0.0f, 0.0f}, self_term[2] = {1.0f, 1.0f};
-      if (!ovf) {
-        const float4 me0 = A[ps.own];
-        float4 me1 = A[ps.own + (two ? 1 : 0)];
-        // a particle whose position has gone NaN (the reference produces such next to boundary particles)
-        // meets nobody, itself included: q is NaN, clamped to 0, for every candidate
-        self_term[0] = (me0.x == me0.x && me0.y == me0.y && me0.z == me0.z) ? 1.0f : 0.0f;
-        self_term[1] = (me1.x == me1.x && me1.y == me1.y && me1.z == me1.z) ? 1.0f : 0.0f;
-        const float two_hh = 2.0f * c.inv_hh;
-        const float sx0 = two_hh * me0.x, sy0 = two_hh * me0.y, sz0 = two_hh * me0.z, a00 = 1.0f + me0.w;
-        const float sx1 = two_hh * me1.x, sy1 = two_hh * me1.y, sz1 = two_hh * me1.z;
-        const float a01 = two ? 1.0f + me1.w : -1.0e30f;  // (an odd one out: its second test meets nobody)
-        // one x-run of candidates (row rr of the staged tile, the 3 cells around the slot's cell), both targets
-        auto sweep_run = [&](int ri, int rr) {
-          int j, je;
-          tile_run(m, rr, lx, j, je);
-          unsigned int mask0 = 0u, mask1 = 0u;
-          auto test4 = [&](int jj) {
+      const float4 me0 = A[ps.own];
+      float4 me1 = A[ps.own + (two ? 1 : 0)];
+      // a particle whose position has gone NaN (the reference produces such next to boundary particles)
+      // meets nobody, itself included: q is NaN, clamped to 0, for every candidate
+      self_term[0] = (me0.x == me0.x && me0.y == me0.y && me0.z == me0.z) ? 1.0f : 0.0f;
+      self_term[1] = (me1.x == me1.x && me1.y == me1.y && me1.z == me1.z) ? 1.0f : 0.0f;
+      const float two_hh = 2.0f * c.inv_hh;
+      const float sx0 = two_hh * me0.x, sy0 = two_hh * me0.y, sz0 = two_hh * me0.z, a00 = 1.0f + me0.w;
+      const float sx1 = two_hh * me1.x, sy1 = two_hh * me1.y, sz1 = two_hh * me1.z;
+      const float a01 = two ? 1.0f + me1.w : -1.0e30f;  // (an odd one out: its second test meets nobody)
+      // one x-run of candidates (row rr of the staged tile, the 3 cells around the slot's cell), both targets
+      auto sweep_run = [&](int ri, int rr) {
+        int j, je;
+        tile_run(m, rr, lx, j, je);
+        unsigned int mask0 = 0u, mask1 = 0u;
+        auto test4 = [&](int jj) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-              const float4 cnd = A[jj + v];
-              if constexpr (WIDE) {  // 1 - r^2/h^2 unclamped against the skin's threshold; nothing is summed
-                const float t0 = __builtin_fmaf(cnd.z, sz0, __builtin_fmaf(cnd.y, sy0, __builtin_fmaf(cnd.x, sx0, cnd.w + a00)));
-                const float t1 = __builtin_fmaf(cnd.z, sz1, __builtin_fmaf(cnd.y, sy1, __builtin_fmaf(cnd.x, sx1, cnd.w + a01)));
-                mask_push_lt(mask0, wide_thr, t0);
-                mask_push_lt(mask1, wide_thr, t1);
-                continue;
-              }
-              const float q0 = fma_clamp01(cnd.z, sz0, __builtin_fmaf(cnd.y, sy0, __builtin_fmaf(cnd.x, sx0, cnd.w + a00)));
-              const float q1 = fma_clamp01(cnd.z, sz1, __builtin_fmaf(cnd.y, sy1, __builtin_fmaf(cnd.x, sx1, cnd.w + a01)));
-              mask_push(mask0, q0);
-              mask_push(mask1, q1);
-              if (v & 1) {
-                accb[0] = __builtin_fmaf(q0, q0, accb[0]);
-                accb[1] = __builtin_fmaf(q1, q1, accb[1]);
-              } else {
-                acc[0] = __builtin_fmaf(q0, q0, acc[0]);
-                acc[1] = __builtin_fmaf(q1, q1, acc[1]);
-              }
+          for (int v = 0; v < 4; ++v) {
+            const float4 cnd = A[jj + v];
+            if constexpr (WIDE) {  // 1 - r^2/h^2 unclamped against the skin's threshold; nothing is summed
+              const float t0 = __builtin_fmaf(cnd.z, sz0, __builtin_fmaf(cnd.y, sy0, __builtin_fmaf(cnd.x, sx0, cnd.w + a00)));
+              const float t1 = __builtin_fmaf(cnd.z, sz1, __builtin_fmaf(cnd.y, sy1, __builtin_fmaf(cnd.x, sx1, cnd.w + a01)));
+              mask_push_lt(mask0, wide_thr, t0);
+              mask_push_lt(mask1, wide_thr, t1);
+              continue;
             }
-          };
-          auto sweep_to = [&](int jend) {  // 8 candidates per trip while they last, then at most one block of 4
-            for (; j + 4 < jend; j += 8) {
-              test4(j);
-              test4(j + 4);
+            const float q0 = fma_clamp01(cnd.z, sz0, __builtin_fmaf(cnd.y, sy0, __builtin_fmaf(cnd.x, sx0, cnd.w + a00)));
+            const float q1 = fma_clamp01(cnd.z, sz1, __builtin_fmaf(cnd.y, sy1, __builtin_fmaf(cnd.x, sx1, cnd.w + a01)));
+            mask_push(mask0, q0);
+            mask_push(mask1, q1);
+            if (v & 1) {
+              accb[0] = __builtin_fmaf(q0, q0, accb[0]);
+              accb[1] = __builtin_fmaf(q1, q1, accb[1]);
+            } else {
+              acc[0] = __builtin_fmaf(q0, q0, acc[0]);
+              acc[1] = __builtin_fmaf(q1, q1, acc[1]);
             }
-            if (j < jend) {
-              test4(j);
-              j += 4;
-            }
-          };
-          const int j32 = j + 32;
-          sweep_to(min(je, j32));
-          nmask[(size_t)ri * mstride + g0] = mask0;
-          if (two) nmask[(size_t)ri * mstride + g0 + 1] = mask1;
-          if (je > j32) {  // a second word for candidates 32-63; a run longer than 64 leaves garbage in it, its valid bit is clear
-            mask0 = mask1 = 0u;
-            sweep_to(je);
-            nmask[(size_t)(kMaskHigh + ri) * mstride + g0] = mask0;
-            if (two) nmask[(size_t)(kMaskHigh + ri) * mstride + g0 + 1] = mask1;
           }
         };
-        if constexpr (!SHARED) {
-          int ri = 0;
-#pragma unroll 1
-          for (int dz = -kTH; dz <= kTH; dz += kTH) {
-#pragma unroll 1
-            for (int dy = -1; dy <= 1; ++dy, ++ri) sweep_run(ri, srow + dz + dy);
+        auto sweep_to = [&](int jend) {  // 8 candidates per trip while they last, then at most one block of 4
+          for (; j + 4 < jend; j += 8) {
+            test4(j);
+            test4(j + 4);
           }
-        } else {
-#pragma unroll 1
-          for (int ri = sub; ri < 9; ri += k) sweep_run(ri, srow + (ri / 3 - 1) * kTH + (ri % 3 - 1));
+          if (j < jend) {
+            test4(j);
+            j += 4;
+          }
+        };
+        const int j32 = j + 32;
+        sweep_to(min(je, j32));
+        nmask[(size_t)ri * mstride + g0] = mask0;
+        if (two) nmask[(size_t)ri * mstride + g0 + 1] = mask1;
+        if (je > j32) {  // a second word for candidates 32-63; a run longer than 64 leaves garbage in it, its valid bit is clear
+          mask0 = mask1 = 0u;
+          sweep_to(je);
+          nmask[(size_t)(kMaskHigh + ri) * mstride + g0] = mask0;
+          if (two) nmask[(size_t)(kMaskHigh + ri) * mstride + g0 + 1] = mask1;
         }
-        acc[0] += accb[0];
-        acc[1] += accb[1];
-      } else if (!WIDE && sub == 0) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          if (e == 1 && !two) break;
-          const int g = g0 + e;
-          const float xi = p.x[g], yi = p.y[g], zi = p.z[g];
-          float a = 0.0f;
-          for_each_grid_candidate(c, cell_start, xi, yi, zi, [&](int j) {
-            if (j == g) return;
-            const float dx = xi - p.x[j], dy = yi - p.y[j], dz = zi - p.z[j];
-            const float r2 = dist2<true>(dx, dy, dz);
-            if (r2 < c.hh) {
-              const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-              a = __builtin_fmaf(c.mass * c.A, q * q, a);
-            }
-          });
-          acc[e] = a;
-        }
-      }
+      };
+      for_each_run<SHARED>(srow, sub, k, sweep_run);
+      acc[0] += accb[0];
+      acc[1] += accb[1];
       if constexpr (WIDE) return;  // (masks only: a tile that overflows the image has none, k_list_build marks its targets)
       if constexpr (SHARED) {
         if (k == 9) {  // (nine adjacent lanes, one run each: for_each_target<.., NINE>)
@@ -1533,20 +1576,11 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
       for (int e = 0; e < 2; ++e) {
         if (e == 1 && !two) break;
         const int g = g0 + e;
-        float a = acc[e];
-        if (!ovf) a = (a - self_term[e]) * (c.mass * c.A);  // the particle met itself once (q = 1)
-        if (bnd.is(g)) {  // a boundary particle reads as density 0, P/rho^2 = 0/0 (Bnd, sph_device.hpp)
-          rho[g] = 0.0f;
-          pterm[g] = __uint_as_float(0x7fc00000u);
-          continue;
-        }
-        rho[g] = a;
-        // (an isolated particle's own term must be a harmless 0 rather than 0/0: see k_density_tiled)
-        const float pr = tait_eos<true>(c, a, c.eos_d0_grad);
-        pterm[g] = a > 0.0f ? dsl_div<true>(pr, a * a) : 0.0f;
+        const float a = (acc[e] - self_term[e]) * (c.mass * c.A);  // the particle met itself once (q = 1)
+        store_density_fast(c, bnd, rho, pterm, g, a);
       }
     });
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------
@@ -2415,34 +2449,17 @@ __global__ __launch_bounds__(kTBlock) void k_pci_density_tiled(DevConsts c, Tile
                                                               Soa3 pv, CSoa3 gterm, Soa3 frc, float* __restrict__ press,
                                                               unsigned int* __restrict__ drift, DevStats* stats) {
   if (stats->pci_done) return;
-  // the LDS image is double-buffered exactly as in k_density_tiled: the next tile's loads are issued behind the
-  // barrier that starts this tile's sweep, committed to the other image by every wave as soon as its own sweep is
-  // over; one barrier per tile (there were three, and the table was fetched in the open)
+  // the LDS image is double-buffered exactly as in k_density_tiled (sweep_tiles_double_buffered): one barrier per tile
+  // (there were three, and the table was fetched in the open)
   __shared__ TileMeta metas[3];
   __shared__ float4 Abuf[2][kTCap];
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   unsigned int ebits = 0u;
   unsigned int n_left = 0u, n_all = 0u;  // queries that have left their particle's tile / all (k_pci_predict_bin)
-  auto load4 = [&](int g, float4* o) {
-    o[0] = load4u(p.x + g);
-    o[1] = load4u(p.y + g);
-    o[2] = load4u(p.z + g);
-  };
-  auto load1 = [&](int g, float* o) {
-    o[0] = p.x[g];
-    o[1] = p.y[g];
-    o[2] = p.z[g];
-  };
+  const LoadPos4 load4{p};
+  const LoadPos1 load1{p};
   auto commit = [&](const TileMeta& mt, const StageRegs<3>& sr, float4* img) {
-    const float ox = __int_as_float(mt.centre[0]), oy = __int_as_float(mt.centre[1]), oz = __int_as_float(mt.centre[2]);
-    stage_commit<3>(mt, sr, load1, [&](int slot, const float* o, bool real) {
-      float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-      if (real) {  // records as in k_density_tiled: tile-relative x, y, z and w = -|x|^2/h^2
-        const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-        v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-      }
-      img[slot] = v;
-    });
+    stage_commit<3>(mt, sr, load1, StoreTileRecord(img, mt, c.inv_hh));
   };
   auto sweep = [&](const TileMeta& m, const float4* __restrict__ A) {
     const int tile = m.tile;
@@ -2484,93 +2501,16 @@ __global__ __launch_bounds__(kTBlock) void k_pci_density_tiled(DevConsts c, Tile
       if (pci_query_escaped(c, qx, qy, qz)) stats->pci_escaped = 1;
       float density;
       if (!ovf && inside) {
-        const float rx = qx - ox, ry = qy - oy, rz = qz - oz;
-        const float two_hh = 2.0f * c.inv_hh;
-        const float sx = two_hh * rx, sy = two_hh * ry, sz = two_hh * rz;
-        const float a0 = 1.0f - c.inv_hh * __builtin_fmaf(rz, rz, __builtin_fmaf(ry, ry, rx * rx));
-        float acc = 0.f, acc1 = 0.f;
-        const int qrow = lz * kTH + ly;
-        // q = clamp(1 - r^2/h^2) = clamp(a0 + w_j + (2/h^2) q.x_j), as in k_density_tiled
-        auto test4 = [&](int jj) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float4 cnd = A[jj + u];
-            const float q = fma_clamp01(cnd.z, sz, __builtin_fmaf(cnd.y, sy, __builtin_fmaf(cnd.x, sx, cnd.w + a0)));
-            if (u & 1) acc1 = __builtin_fmaf(q, q, acc1);
-            else acc = __builtin_fmaf(q, q, acc);
-          }
-        };
-#pragma unroll 1
-        for (int dz = -kTH; dz <= kTH; dz += kTH) {
-#pragma unroll 1
-          for (int dy = -1; dy <= 1; ++dy) {
-            int j, je;
-            tile_run(m, qrow + dz + dy, lx, j, je);
-            for (; j + 4 < je; j += 8) {
-              test4(j);
-              test4(j + 4);
-            }
-            if (j < je) test4(j);
-          }
-        }
-        density = __builtin_fmaf(acc + acc1, c.mass * c.A, c.W0);  // starts at W0, self included
+        const float sum = densityf_tile_sum(m, A, c.inv_hh, qx - ox, qy - oy, qz - oz, lz * kTH + ly, lx);
+        density = __builtin_fmaf(sum, c.mass * c.A, c.W0);  // starts at W0, self included
       } else {
-        density = c.W0;
-        for_each_grid_candidate(c, cell_start, qx, qy, qz, [&](int j) {
-          const float dx = qx - p.x[j], dy = qy - p.y[j], dz = qz - p.z[j];
-          const float r2 = dist2<true>(dx, dy, dz);
-          if (r2 < c.hh) {
-            const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-            density = __builtin_fmaf(c.mass * c.A, q * q, density);
-          }
-        });
+        density = densityf_global(c, cell_start, p, qx, qy, qz);
       }
-      const float density_error = density - c.ref_density;
-      const float abs_err = density_error * __builtin_amdgcn_rcpf(c.ref_density);
-      press[g] += density_error * c.delta;
-      const unsigned int eb = nonneg_bits(abs_err);
-      ebits = eb > ebits ? eb : ebits;
+      pci_accumulate(c, press, g, density, ebits);
     }
   };
   TileFeed feed(desc_of, *n_tiles);
-  int di = 0;
-  bool have = feed.pop(di);
-  if (have) {
-    tile_meta_store(metas[0], tile_meta_request(desc, di));
-    bool have_next = feed.pop(di);
-    int table_word = have_next ? tile_meta_request(desc, di) : 0;
-    sync_lds();  // the first tile's table is visible
-    {
-      StageRegs<3> sr;
-      if (!metas[0].overflow) {
-        stage_issue<3>(metas[0], load4, sr);
-        commit(metas[0], sr, Abuf[0]);
-      }
-    }
-    if (have_next) tile_meta_store(metas[1], table_word);
-    int mc = 0, mn = 1, mnn = 2;  // tables of this tile, the next one, the one after
-    for (int cur = 0; have; cur ^= 1) {
-      sync_lds();  // image `cur` is complete, the next tile's table visible, image `cur ^ 1` and table `mnn` free
-      StageRegs<3> sr;
-      bool have_nn = false, stage_next = false;
-      table_word = 0;
-      if (have_next) {
-        stage_next = metas[mn].overflow == 0;
-        if (stage_next) stage_issue<3>(metas[mn], load4, sr);
-        have_nn = feed.pop(di);
-        if (have_nn) table_word = tile_meta_request(desc, di);
-      }
-      sweep(metas[mc], Abuf[cur]);
-      if (stage_next) commit(metas[mn], sr, Abuf[cur ^ 1]);
-      if (have_nn) tile_meta_store(metas[mnn], table_word);
-      have = have_next;
-      have_next = have_nn;
-      const int t = mc;
-      mc = mn;
-      mn = mnn;
-      mnn = t;
-    }
-  }
+  sweep_tiles_double_buffered<false>(feed, desc, metas, Abuf, load4, commit, sweep);
   wave_atomic_max(&stats->pci_cur_err_bits, ebits);
   pci_drift_add(drift, n_left, n_all);
 }
@@ -2593,26 +2533,10 @@ __global__ __launch_bounds__(kTBlock) void k_pci_density_qtiled(DevConsts c, Til
   __shared__ float4 Abuf[2][kTCap];
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   unsigned int ebits = 0u;
-  auto load4 = [&](int g, float4* o) {
-    o[0] = load4u(p.x + g);
-    o[1] = load4u(p.y + g);
-    o[2] = load4u(p.z + g);
-  };
-  auto load1 = [&](int g, float* o) {
-    o[0] = p.x[g];
-    o[1] = p.y[g];
-    o[2] = p.z[g];
-  };
+  const LoadPos4 load4{p};
+  const LoadPos1 load1{p};
   auto commit = [&](const TileMeta& mt, const StageRegs<3>& sr, float4* img) {
-    const float ox = __int_as_float(mt.centre[0]), oy = __int_as_float(mt.centre[1]), oz = __int_as_float(mt.centre[2]);
-    stage_commit<3>(mt, sr, load1, [&](int slot, const float* o, bool real) {
-      float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-      if (real) {
-        const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-        v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-      }
-      img[slot] = v;
-    });
+    stage_commit<3>(mt, sr, load1, StoreTileRecord(img, mt, c.inv_hh));
   };
   auto sweep = [&](const TileMeta& m, const float4* __restrict__ A) {
     const bool ovf = m.overflow != 0;
@@ -2628,102 +2552,22 @@ __global__ __launch_bounds__(kTBlock) void k_pci_density_qtiled(DevConsts c, Til
         lx = tt.lx;
         qrow = tt.srow;
       } else {  // (no 16-bit cell boundaries to go by: the records of the tile's rows, one row after the other)
-        int ir = 0;
-        ir += (t >= m.tprefix[ir + 8]) ? 8 : 0;
-        ir += (t >= m.tprefix[ir + 4]) ? 4 : 0;
-        ir += (t >= m.tprefix[ir + 2]) ? 2 : 0;
-        ir += (t >= m.tprefix[ir + 1]) ? 1 : 0;
-        rec = qrec[m.trow[ir].x + t];
+        rec = qrec[m.trow[tile_row_of(m.tprefix, t)].x + t];
       }
       const float qx = rec.x, qy = rec.y, qz = rec.z;
       const int g = __float_as_int(rec.w);
       float density;
       if (!ovf) {
-        const float rx = qx - ox, ry = qy - oy, rz = qz - oz;
-        const float two_hh = 2.0f * c.inv_hh;
-        const float sx = two_hh * rx, sy = two_hh * ry, sz = two_hh * rz;
-        const float a0 = 1.0f - c.inv_hh * __builtin_fmaf(rz, rz, __builtin_fmaf(ry, ry, rx * rx));
-        float acc = 0.f, acc1 = 0.f;
-        auto test4 = [&](int jj) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float4 cnd = A[jj + u];
-            const float q = fma_clamp01(cnd.z, sz, __builtin_fmaf(cnd.y, sy, __builtin_fmaf(cnd.x, sx, cnd.w + a0)));
-            if (u & 1) acc1 = __builtin_fmaf(q, q, acc1);
-            else acc = __builtin_fmaf(q, q, acc);
-          }
-        };
-#pragma unroll 1
-        for (int dz = -kTH; dz <= kTH; dz += kTH) {
-#pragma unroll 1
-          for (int dy = -1; dy <= 1; ++dy) {
-            int j, je;
-            tile_run(m, qrow + dz + dy, lx, j, je);
-            for (; j + 4 < je; j += 8) {
-              test4(j);
-              test4(j + 4);
-            }
-            if (j < je) test4(j);
-          }
-        }
-        density = __builtin_fmaf(acc + acc1, c.mass * c.A, c.W0);  // starts at W0, self included
+        const float sum = densityf_tile_sum(m, A, c.inv_hh, qx - ox, qy - oy, qz - oz, qrow, lx);
+        density = __builtin_fmaf(sum, c.mass * c.A, c.W0);  // starts at W0, self included
       } else {
-        density = c.W0;
-        for_each_grid_candidate(c, cell_start, qx, qy, qz, [&](int j) {
-          const float dx = qx - p.x[j], dy = qy - p.y[j], dz = qz - p.z[j];
-          const float r2 = dist2<true>(dx, dy, dz);
-          if (r2 < c.hh) {
-            const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-            density = __builtin_fmaf(c.mass * c.A, q * q, density);
-          }
-        });
+        density = densityf_global(c, cell_start, p, qx, qy, qz);
       }
-      const float density_error = density - c.ref_density;
-      const float abs_err = density_error * __builtin_amdgcn_rcpf(c.ref_density);
-      press[g] += density_error * c.delta;
-      const unsigned int eb = nonneg_bits(abs_err);
-      ebits = eb > ebits ? eb : ebits;
+      pci_accumulate(c, press, g, density, ebits);
     }
   };
   TileFeed feed(nullptr, *n_qtiles);
-  int di = 0;
-  bool have = feed.pop(di);
-  if (have) {
-    tile_meta_store(metas[0], tile_meta_request(desc, di));
-    bool have_next = feed.pop(di);
-    int table_word = have_next ? tile_meta_request(desc, di) : 0;
-    sync_lds();  // the first tile's table is visible
-    {
-      StageRegs<3> sr;
-      if (!metas[0].overflow) {
-        stage_issue<3>(metas[0], load4, sr);
-        commit(metas[0], sr, Abuf[0]);
-      }
-    }
-    if (have_next) tile_meta_store(metas[1], table_word);
-    int mc = 0, mn = 1, mnn = 2;  // tables of this tile, the next one, the one after
-    for (int cur = 0; have; cur ^= 1) {
-      sync_lds();  // image `cur` is complete, the next tile's table visible, image `cur ^ 1` and table `mnn` free
-      StageRegs<3> sr;
-      bool have_nn = false, stage_next = false;
-      table_word = 0;
-      if (have_next) {
-        stage_next = metas[mn].overflow == 0;
-        if (stage_next) stage_issue<3>(metas[mn], load4, sr);
-        have_nn = feed.pop(di);
-        if (have_nn) table_word = tile_meta_request(desc, di);
-      }
-      sweep(metas[mc], Abuf[cur]);
-      if (stage_next) commit(metas[mn], sr, Abuf[cur ^ 1]);
-      if (have_nn) tile_meta_store(metas[mnn], table_word);
-      have = have_next;
-      have_next = have_nn;
-      const int t = mc;
-      mc = mn;
-      mn = mnn;
-      mnn = t;
-    }
-  }
+  sweep_tiles_double_buffered<false>(feed, desc, metas, Abuf, load4, commit, sweep);
   wave_atomic_max(&stats->pci_cur_err_bits, ebits);
 }
 
@@ -2743,80 +2587,18 @@ __global__ __launch_bounds__(kPBlock, 4) void k_pci_density_qpair(DevConsts c, T
   __shared__ float4 A[kTCap];
   const int tid = threadIdx.x;
   unsigned int ebits = 0u;
-  auto load4 = [&](int g, float4* o) {
-    o[0] = load4u(p.x + g);
-    o[1] = load4u(p.y + g);
-    o[2] = load4u(p.z + g);
-  };
-  auto load1 = [&](int g, float* o) {
-    o[0] = p.x[g];
-    o[1] = p.y[g];
-    o[2] = p.z[g];
-  };
-  auto meta_request = [&](int desc_index, int (&w)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = tid + k * kPBlock;
-      w[k] = i < kMetaInts ? desc[(size_t)desc_index * kMetaInts + i] : 0;
-    }
-  };
-  auto meta_store = [&](TileMeta& m, const int (&w)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = tid + k * kPBlock;
-      if (i < kMetaInts) reinterpret_cast<int*>(&m)[i] = w[k];
-    }
-  };
   auto finish = [&](int g, float density) {  // pressure accumulate + the iteration's error (pcisph_darwin.go:76-92)
     if (ROWS && g < 0) return;  // (the tombstone of a query that has moved to another cell's row: k_pci_predict_bin<.., INCR>)
-    const float density_error = density - c.ref_density;
-    const float abs_err = density_error * __builtin_amdgcn_rcpf(c.ref_density);
-    press[g] += density_error * c.delta;
-    const unsigned int eb = nonneg_bits(abs_err);
-    ebits = eb > ebits ? eb : ebits;
+    pci_accumulate(c, press, g, density, ebits);
   };
   TileFeed feed(nullptr, *n_qtiles);
-  int di = 0;
-  bool have = feed.pop(di);
-  if (have) {
-    int w[2];
-    meta_request(di, w);
-    meta_store(metas[0], w);
-  }
-  for (int cur = 0; have; cur ^= 1) {
-    TileMeta& m = metas[cur];
-    sync_lds();  // the previous tile's sweep is over: its LDS records are free, this tile's table is visible
-    have = feed.pop(di);
-    int tw[2] = {0, 0};
-    if (have) meta_request(di, tw);
-    const bool ovf = m.overflow != 0;
+  sweep_tiles_pair<kPBlock>(c, feed, desc, metas, A, p, [&](const TileMeta& m, bool ovf) {
     const float ox = __int_as_float(m.centre[0]), oy = __int_as_float(m.centre[1]), oz = __int_as_float(m.centre[2]);
-    if (!ovf) {
-      auto store = [&](int slot, const float* o, bool real) {
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0e30f);  // pad: q = clamp(-1e30 + ...) = 0
-        if (real) {
-          const float x = o[0] - ox, y = o[1] - oy, z = o[2] - oz;
-          v = make_float4(x, y, z, -c.inv_hh * __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-        }
-        A[slot] = v;
-      };
-      StageRegs<3> sr0, sr1;
-      stage_issue<3>(m, load4, sr0, tid);
-      stage_issue<3>(m, load4, sr1, tid + kPBlock);
-      stage_commit<3>(m, sr0, load1, store, tid);
-      stage_commit<3>(m, sr1, load1, store, tid + kPBlock);
-    }
-    if (have) meta_store(metas[cur ^ 1], tw);
-    sync_lds();
     if (ovf) {
       // (more candidates than the LDS image holds, or more queries than 16 bits count: one query per lane, global memory)
       const int ntarg = m.tprefix[kTB * kTB];
       for (int t = tid; t < ntarg; t += kPBlock) {
-        int ir = 0;
-        ir += (t >= m.tprefix[ir + 8]) ? 8 : 0;
-        ir += (t >= m.tprefix[ir + 4]) ? 4 : 0;
-        ir += (t >= m.tprefix[ir + 2]) ? 2 : 0;
-        ir += (t >= m.tprefix[ir + 1]) ? 1 : 0;
+        const int ir = tile_row_of(m.tprefix, t);
         const int4 w = m.trow[ir];
         size_t at = (size_t)(w.x + t);
         if constexpr (ROWS) {  // (at most 64 x kQueryRow targets: the 16-bit cell boundaries are valid)
@@ -2826,18 +2608,9 @@ __global__ __launch_bounds__(kPBlock, 4) void k_pci_density_qpair(DevConsts c, T
           at = (size_t)(w.x + lx) * kQueryRow + (t - begin);
         }
         const float4 rec = qrec[at];
-        float density = c.W0;
-        for_each_grid_candidate(c, cell_start, rec.x, rec.y, rec.z, [&](int j) {
-          const float dx = rec.x - p.x[j], dy = rec.y - p.y[j], dz = rec.z - p.z[j];
-          const float r2 = dist2<true>(dx, dy, dz);
-          if (r2 < c.hh) {
-            const float q = __builtin_fmaf(-r2, c.inv_hh, 1.0f);
-            density = __builtin_fmaf(c.mass * c.A, q * q, density);
-          }
-        });
-        finish(__float_as_int(rec.w), density);
+        finish(__float_as_int(rec.w), densityf_global(c, cell_start, p, rec.x, rec.y, rec.z));
       }
-      continue;
+      return;
     }
     const int nslots = m.pprefix[kTB * kTB];
     // (nine-lane groups for the remainders, as in k_density_pair: measured neutral here -- 4M PCISPH after 400 steps 1700-1707
@@ -2857,7 +2630,7 @@ __global__ __launch_bounds__(kPBlock, 4) void k_pci_density_qpair(DevConsts c, T
       const float a00 = 1.0f - c.inv_hh * __builtin_fmaf(z0, z0, __builtin_fmaf(y0, y0, x0 * x0));
       const float a01 = two ? 1.0f - c.inv_hh * __builtin_fmaf(z1, z1, __builtin_fmaf(y1, y1, x1 * x1)) : -1.0e30f;
       float acc[2] = {0.0f, 0.0f}, accb[2] = {0.0f, 0.0f};
-      auto sweep_run = [&](int rr) {
+      auto sweep_run = [&](int, int rr) {
         int j, je;
         tile_run(m, rr, lx, j, je);
         auto test4 = [&](int jj) {
@@ -2881,16 +2654,7 @@ __global__ __launch_bounds__(kPBlock, 4) void k_pci_density_qpair(DevConsts c, T
         }
         if (j < je) test4(j);
       };
-      if constexpr (!SHARED) {
-#pragma unroll 1
-        for (int dz = -kTH; dz <= kTH; dz += kTH) {
-#pragma unroll 1
-          for (int dy = -1; dy <= 1; ++dy) sweep_run(srow + dz + dy);
-        }
-      } else {
-#pragma unroll 1
-        for (int ri = sub; ri < 9; ri += k) sweep_run(srow + (ri / 3 - 1) * kTH + (ri % 3 - 1));
-      }
+      for_each_run<SHARED>(srow, sub, k, sweep_run);
       acc[0] += accb[0];
       acc[1] += accb[1];
       if constexpr (SHARED) {
@@ -2903,7 +2667,7 @@ __global__ __launch_bounds__(kPBlock, 4) void k_pci_density_qpair(DevConsts c, T
       finish(__float_as_int(r0.w), __builtin_fmaf(acc[0], c.mass * c.A, c.W0));  // starts at W0, self included
       if (two) finish(__float_as_int(r1.w), __builtin_fmaf(acc[1], c.mass * c.A, c.W0));
     });
-  }
+  });
   wave_atomic_max(&stats->pci_cur_err_bits, ebits);
 }
 

@@ -122,6 +122,95 @@ def test_tile_overflow_falls_back():
     _compare_steps(p, pos, vel, 2, 2e-5, 5e-3, before=crowded)
 
 
+_PCI_OVERFLOW = {}  # variant -> what three PCISPH steps of the overflowing scene left; "oracle" -> the oracle's
+
+
+def _pci_overflow_scene():
+    from dieselfluid_amd import scenes
+    p, pos = scenes.dambreak_scene(12, math_mode=FAST, h_over_dx=5.0)
+    p.pci_max_iters = 4      # (the parameter changes of test_gpu_pci_drift._scene)
+    p.eos_w = p.eos_w / 4
+    p.delta = 1.0e-7
+    p.pci_max_error = -1.0
+    return p, pos
+
+
+def _pci_overflow_run(variant):
+    if variant in _PCI_OVERFLOW:
+        return _PCI_OVERFLOW[variant]
+    p, pos = _pci_overflow_scene()
+    if variant == "oracle":
+        frc = np.tile(np.array(p.force_reset[:], dtype=np.float32), (pos.shape[0], 1))
+        ora = po.OracleSPH.from_state(helpers.oracle_params(p), pos, force=frc)
+        ora.delta = p.delta
+        ora.pcisph_begin()
+        ora.pcisph_step(3)
+        res = (ora.positions(), ora.velocities(), ora.pressures(), float(ora.pci_error))
+    else:
+        eng = _engine(p)
+        if variant:  # (library options, include/dslsph.h: DSL_OPT_PCI_*)
+            k, v = variant.split("=")
+            eng.set_option(k, float(v))
+        eng.pcisph_set_binning(1)
+        eng.upload("positions", pos)
+        eng.reset_forces()
+        eng.pcisph_begin()
+        eng.pcisph_step(3)
+        assert eng.stats().max_cell_count > 36  # 6x6x6 cells x that many records cannot fit the LDS tile
+        res = (eng.download("positions"), eng.download("velocities"), eng.download("pressures"), float(eng.stats().pci_max_error))
+        # the fourth step phase by phase: the accumulator after its first correction iteration, and where it was evaluated
+        eng.pcisph_phase(0)
+        eng.pcisph_phase(1)
+        res += (eng.download("positions"), eng.download("pci_positions"), eng.download("pressures"))
+        eng.pcisph_phase(2)
+        for _ in range(3):
+            eng.pcisph_phase(1)
+            eng.pcisph_phase(2)
+        eng.pcisph_phase(3)
+        assert eng.stats().pci_iters == 4
+        eng.close()
+    _PCI_OVERFLOW[variant] = res
+    return res
+
+
+@pytest.mark.parametrize("variant", ["", "pci_qpair=0", "pci_qrows=0", "pci_qtiled=0"])
+def test_pcisph_tile_overflow_falls_back(variant):
+    """PCISPH, FAST with h = 5 dx, queries binned from the first step: every tile of particles AND every tile of
+    queries exceeds the LDS budget, so each form of the DensityF sweep -- two queries per lane over query rows (the
+    default), over the sorted query array, one query per lane, the global-memory kernel -- takes its overflow path: the
+    row search by the target prefix alone, DensityF from global memory, the pressure accumulate.  Three steps against
+    the oracle, at the FAST tolerances of test_gpu_pci_drift.test_particles_outside_the_grid_keep_their_neighbours.
+    The reference leaves the pressures at zero behind a step, so that comparison only says the library does too; what the
+    overflow paths accumulate is checked inside the fourth step: after its first correction iteration the accumulator
+    of EVERY particle is (rho* - rho0) delta with rho* a float64 brute-force DensityF at the downloaded predicted positions,
+    at the tolerance of test_gpu_pci_drift.test_binned_density_matches_a_float64_brute_force_after_the_drift."""
+    got, want = _pci_overflow_run(variant), _pci_overflow_run("oracle")
+    errs = [helpers.rel_err(got[k], want[k]) for k in range(3)]
+    print(f"{variant!r}: rel. error of positions {errs[0]:.3e}, velocities {errs[1]:.3e}, pressures {errs[2]:.3e}; "
+          f"iteration error {got[3]:.6e} against {want[3]:.6e}")
+    base = _pci_overflow_run("")
+    same = [np.array_equal(got[k].view(np.uint32), base[k].view(np.uint32)) for k in range(3)]
+    diff = [helpers.rel_err(got[k], base[k]) for k in range(3)]
+    print(f"{variant!r} against the default form: same bits {same}, rel. difference {diff}")
+    mid = helpers.rel_err(got[6], base[6])
+    print(f"{variant!r} against the default form, accumulator after one iteration: rel. difference {mid:.3e}")
+    assert np.isfinite(got[0]).all() and np.isfinite(got[2]).all()
+    assert all(same)  # (what the four forms leave behind a step is the same bits: so it is with the parent's kernels)
+    assert errs[0] < 1e-4 and errs[1] < 1e-4 and errs[2] < 1e-4
+    assert abs(got[3] - want[3]) <= 2e-3 * abs(want[3])
+    p, _ = _pci_overflow_scene()
+    h, m = float(p.h), float(p.mass)
+    A = 315.0 / (64.0 * 3.141592653589 * h ** 3)
+    x, xp, press = (got[k].astype(np.float64) for k in (4, 5, 6))
+    d2 = ((xp[:, None, :] - x[None, :, :]) ** 2).sum(axis=2)
+    rho = A + m * A * (np.where(d2 < h * h, 1.0 - d2 / (h * h), 0.0) ** 2).sum(axis=1)
+    acc = (rho - float(p.ref_density)) * float(p.delta)
+    err = np.abs(press - acc).max()
+    print(f"{variant!r}: accumulator after one iteration: max |.| {np.abs(acc).max():.3e}, max error {err:.3e}")
+    assert np.abs(acc).max() > 0.0
+    assert err < 4e-7 * np.abs(acc).max() + 3e-5 * float(p.ref_density) * float(p.delta)
+
+
 def _probe_sets(x, lo, hi, h):
     inside = np.nonzero(np.all((x >= lo) & (x < hi), axis=1))[0]
     near = np.nonzero(np.all((x >= lo - 2 * h) & (x < hi + 2 * h), axis=1))[0]
