@@ -508,6 +508,13 @@ const (
 	OptColliderTriangles = int(C.DSL_OPT_COLLIDER_TRIANGLES)
 	OptCollideHits       = int(C.DSL_OPT_COLLIDE_HITS)
 	OptCollideCull       = int(C.DSL_OPT_COLLIDE_CULL)
+	// the cell index over the collider's triangles (include/dslsph.h)
+	OptCollideIndex        = int(C.DSL_OPT_COLLIDE_INDEX)
+	OptCollideIndexEdge    = int(C.DSL_OPT_COLLIDE_INDEX_EDGE)
+	OptCollideIndexCells   = int(C.DSL_OPT_COLLIDE_INDEX_CELLS)
+	OptCollideIndexEntries = int(C.DSL_OPT_COLLIDE_INDEX_ENTRIES)
+	OptCollideVisits       = int(C.DSL_OPT_COLLIDE_VISITS)
+	OptCollideFullWaves    = int(C.DSL_OPT_COLLIDE_FULL_WAVES)
 )
 
 // SetOption / GetOption: library options (DSL_OPT_* in include/dslsph.h), e.g. the neighbour-list skin of WCSPHStep.

@@ -23,6 +23,9 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-ve
                "-std=c++17", "-Wall"]
 
 
+UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip")
+
+
 class DslError(RuntimeError):
     pass
 
@@ -169,8 +172,9 @@ def build_library(force: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise DslError("hipcc not found: cannot build libdslsph.so (no fallback exists)")
     os.makedirs(os.path.dirname(_BUILT), exist_ok=True)
-    # two translation units: the engine, and the triangle-mesh collider's kernels (csrc/collide.hip)
-    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in ("dslsph.hip", "collide.hip")]
+    # three translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), and the cell index
+    # over its triangles with the kernel that walks it (csrc/collide_index.hip)
+    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in UNITS]
     subprocess.check_call(cmd)
     return _BUILT
 

@@ -1,5 +1,6 @@
-// collide.hpp -- the triangle-mesh collider's device records and the launchers of its kernels.  The kernels
-// (kernels_collide.hpp) are compiled in a translation unit of their own, collide.hip; dslsph.hip includes this header only.
+// collide.hpp -- the triangle-mesh collider's device records and the launchers of its kernels.  The kernels are compiled
+// in translation units of their own -- kernels_collide.hpp in collide.hip, kernels_collide_index.hpp in
+// collide_index.hip; dslsph.hip includes this header only.
 #pragma once
 
 #include "sph_device.hpp"
@@ -33,6 +34,34 @@ struct ColMesh {
   int cull;
 };
 
+// The cell index over the triangles (kernels_collide_index.hpp; DSL_OPT_COLLIDE_INDEX): cubic cells of edge `edge` over
+// [origin, top], the union of the REGULAR triangles' padded boxes.  Cell c lists the regular triangles whose box
+// overlaps it, ascending, in list[start[c] .. start[c + 1]): every segment begins on a multiple of four entries and is
+// filled up with kColNone, so a lane reads its list in aligned 16-byte windows.  `always`: the irregular triangles,
+// ascending -- every wave merges them in.  counters: [0] triangle records loaded, [1] waves that walked the whole list.
+constexpr int kColNone = 0x7f7f7f7f;  // (a byte pattern: the list is filled with hipMemset) past every triangle index
+struct ColIndex {
+  const int* start;  // cells + 1
+  const int* list;
+  const int* always;
+  int n_always;
+  int dims[3];
+  float origin[3], top[3];
+  float edge;
+  unsigned long long* counters;
+};
+// the index's budget: cells, and list entries for T triangles
+constexpr long long kColIndexMaxCells = 1ll << 22;
+constexpr long long col_index_max_entries(long long T) { return 64 * T > (1ll << 20) ? 64 * T : (1ll << 20); }
+// one wave's share of k_index_bounds: over its regular triangles' padded boxes
+struct ColBounds {
+  float lo[3], hi[3];
+  double ext;  // sum over the triangles of the box's mean extent
+  int n_reg;
+  int pad_;
+};
+constexpr int kColBoundsWaves = 256;
+
 // the four returns of Mesh.Collision in HOST order (index = particle id), xyz interleaved; any pointer may be null
 struct ColQuery {
   int* tri;
@@ -46,5 +75,22 @@ void launch_collide_prep(hipStream_t stream, int n_tri, const float* verts, cons
                          TriBox* box, TriBox* chunk);
 // collide: k_collide<respond> over n particle slots.
 void launch_collide(hipStream_t stream, bool respond, int n, float dt, Bnd bnd, ColMesh m, Soa3 p, Soa3 v, ColQuery q, int* hits);
+
+
+// collide_index.hip.  index_bounds: out[kColBoundsWaves], the host combines them in order.  index_total: *total += the
+// cells every regular triangle's box overlaps in the grid of `ix` (dims, origin, top, edge).  index_build: counts into
+// cnt (zeroed, col_index_pad(cells) entries), start (as many) from their scan, segments rounded up to four entries, and
+// *total = start[cells]; the caller allocates list (filled with kColNone) and tmp of that many entries, zeroes cnt again,
+// and index_fill writes the ascending lists (tmp: scratch of the sort) and the always-list (null: none).
+void launch_index_bounds(hipStream_t stream, int n_tri, const TriBox* box, ColBounds* out);
+void launch_index_total(hipStream_t stream, int n_tri, const TriBox* box, ColIndex ix, unsigned long long* total);
+void launch_index_count(hipStream_t stream, int n_tri, const TriBox* box, ColIndex ix, int n_pad, int* cnt, int* start,
+                        unsigned long long* total);
+void launch_index_fill(hipStream_t stream, int n_tri, const TriBox* box, ColIndex ix, int cells, int* cnt, int* list, int* tmp,
+                       int* always);
+int col_index_pad(int cells);  // entries of the count and start arrays for that many cells
+// collide over the index: k_collide_indexed<respond>; m.cull is taken as 1
+void launch_collide_indexed(hipStream_t stream, bool respond, int n, float dt, Bnd bnd, ColMesh m, ColIndex ix, Soa3 p, Soa3 v,
+                            ColQuery q, int* hits);
 
 }  // namespace dsl

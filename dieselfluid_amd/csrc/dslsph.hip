@@ -179,6 +179,14 @@ struct dsl_handle {
   TriBox *col_box = nullptr, *col_chunk = nullptr;
   int* col_hits = nullptr;    // particles the last collide pass moved
   float* col_query = nullptr; // dsl_collider_query's staging: tri, normal, coord, point in host order (10 words per particle)
+  // the cell index over the triangles (kernels_collide_index.hpp; DSL_OPT_COLLIDE_INDEX): col_ix_cells = 0: none
+  bool col_ix_on = false;
+  float col_ix_edge_req = 0.0f;  // DSL_OPT_COLLIDE_INDEX_EDGE; 0: the library's choice
+  ColIndex col_ix{};
+  int col_ix_cells = 0;
+  long long col_ix_entries = 0;
+  size_t col_ix_bytes = 0;         // its share of dev_bytes
+  bool col_last_indexed = false;   // the last collide pass or query ran the indexed kernel
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hpp)
   // timing
@@ -872,18 +880,224 @@ int update_pass(dsl_handle* h, bool use_xs = false) {
   return DSL_OK;
 }
 
+// ---- the cell index over the collider's triangles (kernels_collide_index.hpp; DSL_OPT_COLLIDE_INDEX) ----
+void col_index_free(dsl_handle* h) {
+  (void)hipFree(const_cast<int*>(h->col_ix.start));
+  (void)hipFree(const_cast<int*>(h->col_ix.list));
+  (void)hipFree(const_cast<int*>(h->col_ix.always));
+  (void)hipFree(h->col_ix.counters);
+  h->dev_bytes -= h->col_ix_bytes;
+  h->col_ix = ColIndex{};
+  h->col_ix_bytes = 0;
+  h->col_ix_cells = 0;
+  h->col_ix_entries = 0;
+}
+
+// What an index over the mesh that is set would be: the grid (origin, top, edge, dims of `ix`), its cells and entries.
+struct ColIndexPlan {
+  ColIndex ix{};
+  long long cells = 0, entries = 0;
+  int n_reg = 0;
+};
+
+// The grid for cell edge `edge`: false if it has more than kColIndexMaxCells cells.  dims[k] = the cell of top[k] + 1, by
+// col_cell's expression (the kernels clamp to dims, so the host's rounding of it decides nothing but the grid's size).
+bool col_index_grid(ColIndexPlan* pl, float edge) {
+  double cells = 1.0;
+  for (int k = 0; k < 3; ++k) {
+    const double d = std::floor((double)((pl->ix.top[k] - pl->ix.origin[k]) / edge)) + 1.0;
+    if (!(d >= 1.0 && d <= (double)kColIndexMaxCells)) return false;
+    pl->ix.dims[k] = (int)d;
+    cells *= d;
+  }
+  if (cells > (double)kColIndexMaxCells) return false;
+  pl->ix.edge = edge;
+  pl->cells = (long long)cells;
+  return true;
+}
+
+// Plans the index for cell edge `edge_req` (0: the library's choice) without touching the handle's state.  Blocking.
+// The library's choice: the mean over the regular triangles of their padded box's mean extent, doubled until the grid
+// has at most 2^22 cells and the lists at most max(2^20, 64 T) entries.  An edge the host sets is taken or refused.
+int col_index_plan(dsl_handle* h, float edge_req, ColIndexPlan* pl) {
+  const int T = h->col_tri;
+  ColBounds* dpart = nullptr;
+  unsigned long long* dtotal = nullptr;
+  std::vector<ColBounds> part(kColBoundsWaves);
+  hipError_t e = hipMalloc((void**)&dpart, kColBoundsWaves * sizeof(ColBounds));
+  if (e == hipSuccess) e = hipMalloc((void**)&dtotal, sizeof(unsigned long long));
+  auto done = [&](int rc) {
+    (void)hipFree(dpart);
+    (void)hipFree(dtotal);
+    return rc;
+  };
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return done(fail(h, DSL_ERR_NOMEM, "collider index: hipMalloc failed"));
+  }
+  launch_index_bounds(h->stream, T, h->col_box, dpart);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), dpart, kColBoundsWaves * sizeof(ColBounds), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
+  double ext = 0.0;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (const ColBounds& b : part) {  // (in order: the same sum every time)
+    pl->n_reg += b.n_reg;
+    ext += b.ext;
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::fmin(lo[k], b.lo[k]);
+      hi[k] = std::fmax(hi[k], b.hi[k]);
+    }
+  }
+  const long long budget = col_index_max_entries(T);
+  const std::string budget_text = "the index's budget is 2^22 cells and max(2^20, 64 T) = " + std::to_string(budget) + " list entries";
+  if (pl->n_reg == 0) {  // every triangle is on the always-list: one empty cell
+    for (int k = 0; k < 3; ++k) pl->ix.origin[k] = pl->ix.top[k] = 0.0f, pl->ix.dims[k] = 1;
+    pl->ix.edge = edge_req > 0.0f ? edge_req : 1.0f;
+    pl->cells = 1;
+    pl->entries = T;
+    return done(DSL_OK);
+  }
+  for (int k = 0; k < 3; ++k) pl->ix.origin[k] = lo[k], pl->ix.top[k] = hi[k];
+  auto entries_of = [&](unsigned long long* out) {  // the regular triangles' entries in pl's grid
+    hipError_t e2 = hipMemsetAsync(dtotal, 0, sizeof(unsigned long long), h->stream);
+    if (e2 == hipSuccess) {
+      launch_index_total(h->stream, T, h->col_box, pl->ix, dtotal);
+      e2 = hipGetLastError();
+    }
+    if (e2 == hipSuccess) e2 = hipMemcpyAsync(out, dtotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+    if (e2 == hipSuccess) e2 = hipStreamSynchronize(h->stream);
+    return e2;
+  };
+  unsigned long long reg_entries = 0;
+  if (edge_req > 0.0f) {
+    if (!col_index_grid(pl, edge_req))
+      return done(fail(h, DSL_ERR_INVALID, "DSL_OPT_COLLIDE_INDEX_EDGE: too many cells over this mesh; " + budget_text));
+    if ((e = entries_of(&reg_entries)) != hipSuccess)
+      return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
+    if ((long long)reg_entries + (T - pl->n_reg) > budget)
+      return done(fail(h, DSL_ERR_INVALID, "DSL_OPT_COLLIDE_INDEX_EDGE: too many list entries over this mesh; " + budget_text));
+  } else {
+    float edge = (float)(ext / pl->n_reg);
+    if (!(edge > 0.0f)) edge = 1.0f;
+    for (;; edge *= 2.0f) {
+      if (!std::isfinite(edge)) return done(fail(h, DSL_ERR_INVALID, "collider index: no cell edge fits this mesh; " + budget_text));
+      if (!col_index_grid(pl, edge)) continue;
+      if ((e = entries_of(&reg_entries)) != hipSuccess)
+        return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
+      if ((long long)reg_entries + (T - pl->n_reg) <= budget) break;
+    }
+  }
+  pl->entries = (long long)reg_entries + (T - pl->n_reg);
+  return done(DSL_OK);
+}
+
+// Builds the planned index on the device (any earlier one is freed first).  Blocking.  On failure the handle has no
+// index and the list walk runs.
+int col_index_build(dsl_handle* h, const ColIndexPlan& pl) {
+  col_index_free(h);
+  const int T = h->col_tri, cells = (int)pl.cells, n_always = T - pl.n_reg, n_pad = col_index_pad(cells);
+  ColIndex ix = pl.ix;
+  ix.n_always = n_always;
+  int *start = nullptr, *list = nullptr, *always = nullptr, *cnt = nullptr, *tmp = nullptr;
+  unsigned long long *counters = nullptr, *dtotal = nullptr;
+  size_t bytes = 0;
+  auto fin = [&](int rc) {  // scratch goes either way; the index's own arrays only on failure
+    (void)hipFree(cnt);
+    (void)hipFree(tmp);
+    (void)hipFree(dtotal);
+    if (rc) {
+      (void)hipFree(start);
+      (void)hipFree(list);
+      (void)hipFree(always);
+      (void)hipFree(counters);
+    }
+    return rc;
+  };
+  auto nomem = [&] {
+    (void)hipGetLastError();
+    return fin(fail(h, DSL_ERR_NOMEM, "collider index: hipMalloc failed; the list walk runs"));
+  };
+  auto dev = [&](hipError_t e) { return fin(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e))); };
+  if (hipMalloc((void**)&start, (size_t)n_pad * sizeof(int)) != hipSuccess) return nomem();
+  if (hipMalloc((void**)&cnt, (size_t)n_pad * sizeof(int)) != hipSuccess) return nomem();
+  if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) return nomem();
+  if (hipMalloc((void**)&dtotal, sizeof(unsigned long long)) != hipSuccess) return nomem();
+  if (n_always > 0 && hipMalloc((void**)&always, (size_t)n_always * sizeof(int)) != hipSuccess) return nomem();
+  bytes += (size_t)n_pad * sizeof(int) + 2 * sizeof(unsigned long long) + (size_t)n_always * sizeof(int);
+  ix.start = start;
+  ix.always = always;
+  ix.counters = counters;
+  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n_pad * sizeof(int), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), h->stream);
+  unsigned long long padded = 0;
+  if (e == hipSuccess) {
+    launch_index_count(h->stream, T, h->col_box, ix, n_pad, cnt, start, dtotal);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&padded, dtotal, sizeof(padded), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return dev(e);
+  if (padded > 0x7fffffffull) return fin(fail(h, DSL_ERR_NOMEM, "collider index: the cell lists pass 2^31 entries; the list walk runs"));
+  const size_t n_list = (size_t)std::max<unsigned long long>(padded, 4);
+  if (hipMalloc((void**)&list, n_list * sizeof(int)) != hipSuccess) return nomem();
+  if (hipMalloc((void**)&tmp, n_list * sizeof(int)) != hipSuccess) return nomem();
+  bytes += n_list * sizeof(int);
+  ix.list = list;
+  e = hipMemsetAsync(list, kColNone & 0xff, n_list * sizeof(int), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)n_pad * sizeof(int), h->stream);
+  if (e == hipSuccess) {
+    launch_index_fill(h->stream, T, h->col_box, ix, cells, cnt, list, tmp, always);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return dev(e);
+  h->col_ix = ix;
+  h->col_ix_cells = cells;
+  h->col_ix_entries = pl.entries;
+  h->col_ix_bytes = bytes;
+  h->dev_bytes += bytes;
+  return fin(DSL_OK);
+}
+
+// The index follows the mesh, the option and the edge: called when any of them has changed.  A refused edge
+// (DSL_ERR_INVALID) leaves the index that was built.
+int col_index_update(dsl_handle* h, bool on, float edge_req) {
+  if (!on || h->col_tri == 0) {
+    col_index_free(h);
+    return DSL_OK;
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the index that is replaced)
+  ColIndexPlan pl;
+  if (int rc = col_index_plan(h, edge_req, &pl)) return rc;
+  return col_index_build(h, pl);
+}
+
 // The collider pass (kernels_collide.hpp): Mesh.Collision for every fluid particle, then the build-defined response, in
 // place on the current state.  Without a mesh nothing is launched.  dsl_stats.max_vel / max_f stay what Update saw.
 ColMesh col_mesh(const dsl_handle* h) {
   return ColMesh{h->col_rec, h->col_box, h->col_chunk, h->col_tri, h->col_s_thr, h->col_rest, h->col_cull ? 1 : 0};
 }
+// The launch of either collide kernel: the walk over the cell index if one is built and the broad phase is on (cull 0
+// keeps meaning "every pair is tested"), the list walk otherwise.
+int collide_launch(dsl_handle* h, bool respond, ColQuery q, int* hits) {
+  h->col_last_indexed = h->col_ix_cells > 0 && h->col_cull;
+  if (h->col_last_indexed) {
+    HIP_TRY(h, hipMemsetAsync(h->col_ix.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+    launch_collide_indexed(h->stream, respond, h->n, h->c.dt, bnd_of(h), col_mesh(h), h->col_ix, mpos(h, h->cur_pv),
+                           mvel(h, h->cur_pv), q, hits);
+  } else {
+    launch_collide(h->stream, respond, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), q, hits);
+  }
+  return DSL_OK;
+}
 int collide_pass(dsl_handle* h) {
   if (h->col_tri == 0) return DSL_OK;
   HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
-  int rc = timed(h, DSL_K_COLLIDE, [&] {
-    launch_collide(h->stream, true, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), ColQuery{},
-                   h->col_hits);
-  });
+  int lrc = DSL_OK;
+  int rc = timed(h, DSL_K_COLLIDE, [&] { lrc = collide_launch(h, true, ColQuery{}, h->col_hits); });
+  if (lrc) return lrc;
   if (rc) return rc;
   h->grid_valid = false;  // positions moved
   h->masks_valid = false;
@@ -986,6 +1200,7 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->col_chunk);
   (void)hipFree(h->col_hits);
   (void)hipFree(h->col_query);
+  col_index_free(h);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1902,6 +2117,25 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
       h->pci_rows_live = false;
       return DSL_OK;
     case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
+    // the cell index over the collider's triangles: built (blocking) as soon as option, edge and mesh are all there; an
+    // edge that breaks the budget is refused and leaves option, edge and index as they were
+    case DSL_OPT_COLLIDE_INDEX: {
+      const bool on = value != 0.0;
+      if (on == h->col_ix_on) return DSL_OK;
+      const int rc = col_index_update(h, on, h->col_ix_edge_req);
+      if (rc != DSL_ERR_INVALID) h->col_ix_on = on;
+      return rc;
+    }
+    case DSL_OPT_COLLIDE_INDEX_EDGE: {
+      const float edge = (float)value;
+      if (!(value >= 0.0) || !std::isfinite(edge) || (value > 0.0 && !(edge > 0.0f)))
+        return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_INDEX_EDGE is a positive finite cell edge within the index's "
+                                        "budget (2^22 cells, max(2^20, 64 T) list entries), or 0 for the library's choice");
+      int rc = DSL_OK;
+      if (h->col_ix_on && h->col_tri > 0 && edge != h->col_ix_edge_req) rc = col_index_update(h, true, edge);
+      if (rc != DSL_ERR_INVALID) h->col_ix_edge_req = edge;
+      return rc;
+    }
     default:
       return fail(h, DSL_ERR_INVALID, "dsl_set_option: unknown or read-only option");
   }
@@ -1949,6 +2183,22 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
       *value = (double)hits;
       return DSL_OK;
     }
+    case DSL_OPT_COLLIDE_INDEX: *value = h->col_ix_on ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDE_INDEX_EDGE: *value = h->col_ix_cells > 0 ? (double)h->col_ix.edge : 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDE_INDEX_CELLS: *value = (double)h->col_ix_cells; return DSL_OK;
+    case DSL_OPT_COLLIDE_INDEX_ENTRIES: *value = (double)h->col_ix_entries; return DSL_OK;
+    case DSL_OPT_COLLIDE_VISITS:
+    case DSL_OPT_COLLIDE_FULL_WAVES: {  // (blocking: the kernel counts on the device); -1: the list walk ran, or nothing
+      unsigned long long ctr[2] = {0, 0};
+      if (!h->col_last_indexed || h->col_ix_cells == 0) {
+        *value = -1.0;
+        return DSL_OK;
+      }
+      HIP_TRY(h, hipMemcpyAsync(ctr, h->col_ix.counters, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      *value = (double)ctr[option == DSL_OPT_COLLIDE_VISITS ? 0 : 1];
+      return DSL_OK;
+    }
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }
@@ -1961,8 +2211,11 @@ int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* nor
   CHECK_HANDLE(h);
   if (h->c.slab_axis >= 0 || h->c.n_ptr)
     return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_set_mesh: a collider mesh is not supported in slab mode");
-  if (n_triangles == 0) {  // removes the mesh (the arrays stay for the next one)
+  if (n_triangles == 0) {  // removes the mesh (the arrays stay for the next one; the cell index goes)
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->col_tri = 0;
+    h->col_last_indexed = false;
+    col_index_free(h);
     return DSL_OK;
   }
   if (!vertices || !normals) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: null vertex or normal pointer");
@@ -1970,6 +2223,8 @@ int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* nor
   const int T = (int)n_triangles, nchunk = (T + kColChunk - 1) / kColChunk;
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the mesh that is replaced)
   h->col_tri = 0;  // no mesh until the new one is whole: a failure below leaves the handle without a collider
+  h->col_last_indexed = false;
+  col_index_free(h);
   if (T > h->col_alloc) {
     (void)hipFree(h->col_rec);
     (void)hipFree(h->col_box);
@@ -2013,7 +2268,8 @@ int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* nor
   h->col_radius = radius;
   h->col_rest = restitution;
   h->col_tri = T;
-  return DSL_OK;
+  // the cell index, if it is switched on: a failure here leaves the mesh set, without an index (the list walk runs)
+  return col_index_update(h, h->col_ix_on, h->col_ix_edge_req);
 }
 
 int dsl_collide_pass(dsl_handle* h) {
@@ -2037,7 +2293,7 @@ int dsl_collider_query(dsl_handle* h, int32_t* tri, float* normal, float* coord,
   float* qb = h->col_query;
   const ColQuery q{tri ? reinterpret_cast<int*>(qb) : nullptr, normal ? qb + nf : nullptr, coord ? qb + 4 * nf : nullptr,
                    point ? qb + 7 * nf : nullptr, h->ids[h->cur_ids]};
-  launch_collide(h->stream, false, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), q, nullptr);
+  if (int rc = collide_launch(h, false, q, nullptr)) return rc;
   HIP_TRY(h, hipGetLastError());
   if (tri) HIP_TRY(h, hipMemcpyAsync(tri, q.tri, nf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (normal) HIP_TRY(h, hipMemcpyAsync(normal, q.normal, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));

@@ -14,14 +14,9 @@
 // the host layer reaches them through the launchers of collide.hpp.
 #pragma once
 
-#include "collide.hpp"
+#include "collide_narrow.hpp"  // col_dot, wave_uniform, col_narrow, col_finish: shared with kernels_collide_index.hpp
 
 namespace dsl {
-
-__device__ __forceinline__ float col_dot(float x0, float x1, float x2, float y0, float y1, float y2) {
-  const float t0 = x0 * y0, t1 = x1 * y1, t2 = x2 * y2;
-  return (t0 + t1) + t2;
-}
 
 // Which triangles may the broad phase skip?  For a particle with |V| >= 1e-4 a hit needs |V k| <= r (up to rounding), and
 // |V k| = |V| |d| / |n.V| >= |d| / |n| -- or, with n.V == 0 and the 0.0001 substitute, |V| |d| / 1e-4 >= |d|: the particle
@@ -100,9 +95,6 @@ __global__ __launch_bounds__(64) void k_collide_chunks(int n_tri, const TriBox* 
   chunk[ch] = U;
 }
 
-__device__ __forceinline__ float wave_uniform(float v) {
-  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-}
 __device__ __forceinline__ float wave_min(float v) {
   for (int off = kWave / 2; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, kWave));
   return wave_uniform(v);
@@ -112,9 +104,7 @@ __device__ __forceinline__ float wave_max(float v) {
   return wave_uniform(v);
 }
 
-// RESPOND = false: the query (writes `q`, leaves the particles alone).  RESPOND = true: the build-defined response -- a
-// colliding particle with k >= 0 (the plane lies ahead along V) goes back to `point` and its velocity is reflected,
-// v <- v - n ((1 + e) (v.n)); a receding one (k < 0) is left alone -- and `hits` counts the particles moved.
+// RESPOND: collide_narrow.hpp, col_finish.
 template <bool RESPOND>
 __global__ __launch_bounds__(kColBlock) void k_collide(int n, float dt, Bnd bnd, ColMesh m, Soa3 p, Soa3 v, ColQuery q,
                                                     int* __restrict__ hits) {
@@ -150,8 +140,7 @@ __global__ __launch_bounds__(kColBlock) void k_collide(int n, float dt, Bnd bnd,
                               whi[2] < B.lo[2] || wlo[2] > B.hi[2]);
   };
 
-  int hit = -1;
-  float hk = 0.f, hu = 0.f, hv = 0.f, hw = 0.f, hnx = 0.f, hny = 0.f, hnz = 0.f;
+  ColHit hit;
   for (int cb = 0; cb < m.n_tri; cb += kColChunk) {
     if (__ballot(todo) == 0ull) break;  // every lane has hit or stands still
     if (cull && skippable(m.chunk[cb / kColChunk])) continue;
@@ -160,78 +149,11 @@ __global__ __launch_bounds__(kColBlock) void k_collide(int n, float dt, Bnd bnd,
       if (__ballot(todo) == 0ull) break;
       if (cull && skippable(m.box[t])) continue;
       const TriRec R = m.rec[t];  // wave-uniform
-      if (todo) {
-        float ndr = col_dot(R.n[0], R.n[1], R.n[2], vx, vy, vz);
-        if (ndr == 0.0f) ndr = 0.0001f;
-        const float d = col_dot(R.a[0] - px, R.a[1] - py, R.a[2] - pz, R.n[0], R.n[1], R.n[2]);
-        const float k = d / ndr;
-        const float sx = vx * k, sy = vy * k, sz = vz * k;
-        const float p0x = px + sx, p0y = py + sy, p0z = pz + sz;
-        const float qx = px - p0x, qy = py - p0y, qz = pz - p0z;
-        const float s = col_dot(qx, qy, qz, qx, qy, qz);
-        if (s <= m.s_thr) {  // dist <= r (false for NaN)
-          const float wx = px - R.a[0], wy = py - R.a[1], wz = pz - R.a[2];
-          const float d20 = col_dot(wx, wy, wz, R.e0[0], R.e0[1], R.e0[2]);
-          const float d21 = col_dot(wx, wy, wz, R.e1[0], R.e1[1], R.e1[2]);
-          const float a0 = R.d11 * d20, a1 = R.d01 * d21, b0 = R.d00 * d21, b1 = R.d01 * d20;
-          const float bu = (a0 - a1) / R.denom;
-          const float bv = (b0 - b1) / R.denom;
-          const float bw = (1.0f - bv) - bu;
-          const float bs = (bu + bv) + bw;
-          if (bu <= 1.0f && bv <= 1.0f && bw <= 1.0f && bs <= 1.0f && bu >= 0.0f && bv >= 0.0f && bw >= 0.0f) {
-            hit = t;  // the first triangle in list order wins (mesh.go:48-53)
-            hk = k;
-            hu = bu;
-            hv = bv;
-            hw = bw;
-            hnx = R.n[0];
-            hny = R.n[1];
-            hnz = R.n[2];
-            todo = false;
-          }
-        }
-      }
+      if (todo && col_narrow(R, t, m.s_thr, px, py, pz, vx, vy, vz, hit)) todo = false;
     }
   }
 
-  // point = P + V (-dt): the position rewound (tri.go:70)
-  const float mdt = -dt;
-  const float bx = px + vx * mdt, by = py + vy * mdt, bz = pz + vz * mdt;
-  if constexpr (RESPOND) {
-    const bool moved = hit >= 0 && hk >= 0.0f;
-    if (moved) {
-      const float f = (1.0f + m.rest) * col_dot(vx, vy, vz, hnx, hny, hnz);
-      p.x[i] = bx;
-      p.y[i] = by;
-      p.z[i] = bz;
-      v.x[i] = vx - hnx * f;
-      v.y[i] = vy - hny * f;
-      v.z[i] = vz - hnz * f;
-    }
-    const unsigned long long mm = __ballot(moved);
-    if (mm != 0ull && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(hits, (int)__popcll(mm));
-  } else {
-    if (live) {
-      const size_t o = (size_t)q.ids[i];
-      const bool h = hit >= 0;
-      if (q.tri) q.tri[o] = hit;
-      if (q.normal) {
-        q.normal[3 * o] = h ? hnx : 0.f;
-        q.normal[3 * o + 1] = h ? hny : 0.f;
-        q.normal[3 * o + 2] = h ? hnz : 0.f;
-      }
-      if (q.coord) {
-        q.coord[3 * o] = h ? hu : 0.f;
-        q.coord[3 * o + 1] = h ? hv : 0.f;
-        q.coord[3 * o + 2] = h ? hw : 0.f;
-      }
-      if (q.point) {
-        q.point[3 * o] = h ? bx : 0.f;
-        q.point[3 * o + 1] = h ? by : 0.f;
-        q.point[3 * o + 2] = h ? bz : 0.f;
-      }
-    }
-  }
+  col_finish<RESPOND>(i, live, dt, m.rest, hit, px, py, pz, vx, vy, vz, p, v, q, hits);
 }
 
 }  // namespace dsl

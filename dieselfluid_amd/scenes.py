@@ -193,3 +193,30 @@ def box_mesh(center, size, subdiv: int = 1):
             vs.append(v)
             ns.append(n)
     return np.concatenate(vs), np.concatenate(ns)
+
+
+def icosphere_mesh(center, radius: float, level: int = 0):
+    """(vertices, normals) of a sphere obstacle: the icosahedron, every triangle split in four `level` times and the new
+    vertices pushed out to the sphere -- 20 * 4^level triangles (20,480 at level 5), none of them thin (a latitude /
+    longitude sphere ends in needles at its poles, which a collider's broad phase cannot skip).  The normals are the unit
+    outward face normals, computed in float64 from the float32 vertices."""
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = np.array([(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+                  (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)], dtype=np.float64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    faces = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2),
+                      (10, 7, 6), (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11),
+                      (6, 2, 10), (8, 6, 7), (9, 8, 1)], dtype=np.int64)
+    tri = v[faces]  # (20, 3, 3), counter-clockwise seen from outside
+    for _ in range(int(level)):
+        a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+        ab, bc, ca = a + b, b + c, c + a
+        ab, bc, ca = (m / np.linalg.norm(m, axis=1, keepdims=True) for m in (ab, bc, ca))
+        tri = np.stack([np.stack(q, axis=1) for q in ((a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca))], axis=1).reshape(-1, 3, 3)
+    verts = (np.asarray(center, dtype=np.float64)[None, None, :] + float(radius) * tri).astype(f32)
+    q = verts.astype(np.float64)
+    n = np.cross(q[:, 1] - q[:, 0], q[:, 2] - q[:, 0])
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    outward = np.sum(n * (q.mean(axis=1) - np.asarray(center, dtype=np.float64)[None, :]), axis=1) > 0
+    assert outward.all()
+    return verts, n.astype(f32)

@@ -523,9 +523,24 @@ enum {
                                      has changed cells is moved (default 1; 0: every iteration fills the rows afresh) */
   DSL_OPT_COLLIDER_TRIANGLES = 32, /* (get) triangles of the collider mesh; 0: none */
   DSL_OPT_COLLIDE_HITS = 33,       /* (get, blocking) particles the last collide pass moved (counted by the kernel) */
-  DSL_OPT_COLLIDE_CULL = 34        /* (set/get, default 1) broad phase: a wave skips a triangle -- a chunk of 256 by its box -- that
+  DSL_OPT_COLLIDE_CULL = 34,       /* (set/get, default 1) broad phase: a wave skips a triangle -- a chunk of 256 by its box -- that
                                       none of its particles can reach (csrc/kernels_collide.hpp states when); 0: every pair is
                                       tested.  Results are identical either way */
+  /* A uniform-grid index over the collider's triangles (csrc/kernels_collide_index.hpp): a wave visits only the triangles
+   * some lane of it could hit, in list order; results are the list walk's, bit for bit.  Built on the device (blocking)
+   * inside dsl_collider_set_mesh while the option is on, and when option or edge change while a mesh is set; its memory is
+   * counted in DSL_OPT_DEVICE_BYTES and freed with the mesh.  Budget: 2^22 cells, max(2^20, 64 T) list entries.  An edge
+   * outside the budget, negative or non-finite is refused (DSL_ERR_INVALID; option, edge and index stay as they were --
+   * from dsl_collider_set_mesh: the new mesh is set, without an index).  If the build fails on the device (DSL_ERR_NOMEM)
+   * the mesh stays set, there is no index, and the list walk runs.  Used only while DSL_OPT_COLLIDE_CULL is 1. */
+  DSL_OPT_COLLIDE_INDEX = 35,         /* (set/get, default 0) 0: the list walk; 1: the walk over the index */
+  DSL_OPT_COLLIDE_INDEX_EDGE = 36,    /* (set/get) cell edge; 0 (default): the library's choice -- the mean extent of the regular
+                                         triangles' padded boxes, doubled until the budget holds.  get: the edge in use, 0: no index */
+  DSL_OPT_COLLIDE_INDEX_CELLS = 37,   /* (get) cells of the built index; 0: none */
+  DSL_OPT_COLLIDE_INDEX_ENTRIES = 38, /* (get) cell-list entries plus always-list entries (the irregular triangles) */
+  DSL_OPT_COLLIDE_VISITS = 39,        /* (get, blocking) triangle records loaded, summed over the waves of the last collide pass or
+                                         query that the indexed kernel ran (full-walk waves included); -1: the list walk ran it */
+  DSL_OPT_COLLIDE_FULL_WAVES = 40     /* (get, blocking) waves of that launch that walked the whole list (a slow lane); -1 likewise */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
