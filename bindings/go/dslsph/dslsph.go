@@ -610,6 +610,50 @@ func (e *Engine) SlabImageShift(fromLo, fromHi float32) error {
 	return e.ck(C.dsl_slab_image_shift(e.h, C.float(fromLo), C.float(fromHi)))
 }
 
+// Re-balancing: the slab planes move during a run (include/dslsph.h; DESIGN.md 6).  SlabRebalance hands it to the native
+// step drivers: every = M > 0 steps between looks, 0 = off; planes and their bounds in cell layers from origin, one entry
+// per rank plus one, identical on every rank.
+func (e *Engine) SlabRebalance(every int, origin float32, nLayers int, planes, planeMin, planeMax []int32, minLayers int) error {
+	var p, lo, hi *C.int32_t
+	if every > 0 {
+		if len(planes) < 2 || len(planeMin) != len(planes) || len(planeMax) != len(planes) {
+			return errors.New("dslsph: SlabRebalance wants planes, planeMin and planeMax of ranks + 1 entries each")
+		}
+		p, lo, hi = (*C.int32_t)(unsafe.Pointer(&planes[0])), (*C.int32_t)(unsafe.Pointer(&planeMin[0])), (*C.int32_t)(unsafe.Pointer(&planeMax[0]))
+	}
+	return e.ck(C.dsl_slab_rebalance(e.h, C.int(every), C.float(origin), C.int(nLayers), p, lo, hi, C.int(minLayers)))
+}
+
+// SlabRebalanceState: the planes of the last plan (ranks + 1), the last global histogram (nLayers), looks and plane moves
+// so far.  Blocking.
+func (e *Engine) SlabRebalanceState(ranks, nLayers int) (planes, counts []int32, looks, moves int64, err error) {
+	planes, counts = make([]int32, ranks+1), make([]int32, nLayers)
+	var l, m C.int64_t
+	var cp *C.int32_t
+	if nLayers > 0 {
+		cp = (*C.int32_t)(unsafe.Pointer(&counts[0]))
+	}
+	err = e.ck(C.dsl_slab_rebalance_state(e.h, (*C.int32_t)(unsafe.Pointer(&planes[0])), cp, &l, &m))
+	return planes, counts, int64(l), int64(m), err
+}
+
+// SlabPlanes: the planes in force (a host that classifies particles itself needs them once planes move).
+func (e *Engine) SlabPlanes() (lo, hi float32, err error) {
+	var l, h C.float
+	err = e.ck(C.dsl_slab_get_planes(e.h, &l, &h))
+	return float32(l), float32(h), err
+}
+
+// The building blocks, for a host that runs the exchange itself: owned particles per cell layer into nLayers int32 words of
+// device memory (asynchronous), and new planes without touching the particles -- legal only between an integrate and the next
+// pack.
+func (e *Engine) SlabLayerCounts(origin float32, nLayers int, devCounts unsafe.Pointer) error {
+	return e.ck(C.dsl_slab_layer_counts(e.h, C.float(origin), C.int(nLayers), (*C.int32_t)(devCounts)))
+}
+func (e *Engine) SlabMovePlanes(lo, hi float32) error {
+	return e.ck(C.dsl_slab_move_planes(e.h, C.float(lo), C.float(hi)))
+}
+
 // PCISPHErrorWord: copy the iteration's max density error out to / back in from a device word of the caller's
 // (the all-reduce between DSL_PCI_ITERATE and DSL_PCI_CHECK of a host-driven slab step).
 func (e *Engine) PCISPHErrorWord(devWord unsafe.Pointer, store bool) error {

@@ -23,7 +23,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-ve
                "-std=c++17", "-Wall"]
 
 
-UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip")
+UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip", "slab_balance.hip")
 
 
 class DslError(RuntimeError):
@@ -146,6 +146,11 @@ EXPORTS = {
     "dsl_slab_replan": (C.c_int, [_vp]),
     "dsl_slab_wcsph_step": (C.c_int, [_vp, C.c_int]),
     "dsl_slab_pcisph_step": (C.c_int, [_vp, C.c_int]),
+    "dsl_slab_layer_counts": (C.c_int, [_vp, C.c_float, C.c_int, _vp]),
+    "dsl_slab_move_planes": (C.c_int, [_vp, C.c_float, C.c_float]),
+    "dsl_slab_get_planes": (C.c_int, [_vp, _fp, _fp]),
+    "dsl_slab_rebalance": (C.c_int, [_vp, C.c_int, C.c_float, C.c_int, _ip, _ip, _ip, C.c_int]),
+    "dsl_slab_rebalance_state": (C.c_int, [_vp, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dsl_set_option": (C.c_int, [_vp, C.c_int, C.c_double]),
     "dsl_get_option": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),
     "dsl_set_ids": (C.c_int, [_vp, _ip, C.c_size_t]),
@@ -172,8 +177,9 @@ def build_library(force: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise DslError("hipcc not found: cannot build libdslsph.so (no fallback exists)")
     os.makedirs(os.path.dirname(_BUILT), exist_ok=True)
-    # three translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), and the cell index
-    # over its triangles with the kernel that walks it (csrc/collide_index.hip)
+    # four translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), the cell index over
+    # its triangles with the kernel that walks it (csrc/collide_index.hip), and the slab re-balancing count
+    # (csrc/slab_balance.hip)
     cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in UNITS]
     subprocess.check_call(cmd)
     return _BUILT

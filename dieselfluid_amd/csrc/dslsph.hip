@@ -2985,6 +2985,7 @@ int dsl_slab_detach(dsl_handle* h) {
     (void)hipFree(L->recv[k]);
   }
   (void)hipFree(L->dev_words);
+  (void)hipFree(L->bal.dev_counts);
   if (L->ev_pack) (void)hipEventDestroy(L->ev_pack);
   if (L->ev_xfer) (void)hipEventDestroy(L->ev_xfer);
   if (L->comm_stream) (void)hipStreamDestroy(L->comm_stream);
@@ -3106,6 +3107,74 @@ int link_exchange(dsl_handle* h) {
   return link_append(h);
 }
 
+// ---- re-balancing: the slab planes move with the particles (dsl_slab_rebalance) ----
+// where layer plane k lies: the one expression every check and every move uses
+static float balance_plane(const dsl_handle* h, float origin, int k) { return origin + (float)k * h->c.cell; }
+
+// is `x` on a cell plane of the handle's grid along the slab axis (1e-3 cell of slack, as update_split allows)?
+static bool on_cell_plane(const dsl_handle* h, float x) {
+  const float f = (x - h->c.gmin[h->c.slab_axis]) * h->c.inv_cell;
+  return std::fabs(f - std::nearbyint(f)) <= 1.0e-3f;
+}
+
+// the fullest layer next to an interior plane in the last global histogram; -1 before the first look
+static long long balance_adjacent_max(const SlabBalance& B) {
+  if (B.counts.empty()) return -1;
+  long long m = 0;
+  for (int r = 1; r < B.nranks; ++r)
+    for (int k = B.planes[(size_t)r] - 1; k <= B.planes[(size_t)r]; ++k)
+      if (k >= 0 && k < B.n_layers && B.counts[(size_t)k] > m) m = B.counts[(size_t)k];
+  return m;
+}
+
+// owned particles per layer into dev_counts (overwritten), on the handle's stream
+static int layer_counts_on(dsl_handle* h, float origin, int n_layers, int32_t* dev_counts) {
+  HIP_TRY(h, hipMemsetAsync(dev_counts, 0, sizeof(int32_t) * (size_t)n_layers, h->stream));
+  launch_slab_layer_count(h->stream, h->c, launch_n(h), cpos(h), origin, n_layers, dev_counts);
+  HIP_TRY(h, hipGetLastError());
+  return DSL_OK;
+}
+
+// new planes on the host; the particles are not touched.  Between an integrate and the pack that follows it ownership
+// is positional among the live particles (every ghost is NaN): whoever lies outside the new planes leaves as a migrant.
+static void move_planes(dsl_handle* h, float lo, float hi) {
+  h->c.slab_lo = lo;
+  h->c.slab_hi = hi;
+  update_split(h);
+  h->grid_valid = false;  // the owning / band / interior tile lists are made by the neighbour build
+}
+
+// The look: count, one MAX all-reduce over n_layers words (the ranks' histograms are disjoint -- one owner per live
+// particle, planes on layer boundaries -- so the MAX of the non-negative counts is their sum), one host synchronisation,
+// the plan.  A plan that moves a plane is applied by the NEXT step, between its integrate and its pack.
+static int balance_look(dsl_handle* h) {
+  SlabLink& L = *h->link;
+  SlabBalance& B = L.bal;
+  if (int rc = layer_counts_on(h, B.origin, B.n_layers, B.dev_counts)) return rc;
+  if (L.comm && L.comm->nranks > 1)
+    if (int rc = xfer_all_reduce_max(h, L.comm, B.dev_counts, (size_t)B.n_layers, h->stream)) return rc;
+  B.counts.resize((size_t)B.n_layers);
+  HIP_TRY(h, hipMemcpyAsync(B.counts.data(), B.dev_counts, sizeof(int32_t) * (size_t)B.n_layers, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  std::vector<int32_t> next(B.planes.size());
+  const int moved = slab_plan_planes(B.counts.data(), B.n_layers, B.nranks, B.planes.data(), B.plane_min.data(),
+                                     B.plane_max.data(), B.min_layers, next.data());
+  B.planes.swap(next);
+  B.pending = B.pending || moved > 0;
+  B.moves += moved;
+  B.looks++;
+  return DSL_OK;
+}
+
+static void balance_apply(dsl_handle* h) {
+  SlabBalance& B = h->link->bal;
+  B.pending = false;
+  // (a domain end stays where dsl_slab_config put it: -INFINITY / INFINITY, usually)
+  const float lo = B.rank > 0 ? balance_plane(h, B.origin, B.planes[(size_t)B.rank]) : h->c.slab_lo;
+  const float hi = B.rank + 1 < B.nranks ? balance_plane(h, B.origin, B.planes[(size_t)B.rank + 1]) : h->c.slab_hi;
+  move_planes(h, lo, hi);
+}
+
 // every rank learns the largest band counts (and any overflow) seen anywhere since the last
 // re-plan; all ranks switch to the same new message capacities.  Blocking.
 int link_replan(dsl_handle* h) {
@@ -3125,7 +3194,15 @@ int link_replan(dsl_handle* h) {
                     "enlarge cap_full / cap_xonly / dsl_params.capacity");
   if (st[1] != 0)
     return fail(h, DSL_ERR_OVERFLOW, "split slab step: a particle outran the margin on some rank (ghosts were missed); enlarge the margin");
-  const long long want_full = (long long)(1.15 * st[2]) + 1024, want_x = (long long)(1.15 * st[3]) + 1024;
+  long long want_full = (long long)(1.15 * st[2]) + 1024;
+  const long long want_x = (long long)(1.15 * st[3]) + 1024;
+  if (L.bal.every > 0) {
+    // a plane that moves sends one cell layer of migrants on top of the h band: room for the fullest layer next to an
+    // interior plane, by the last global histogram (the same numbers on every rank); before the first look there is
+    // none, and the capacity the host attached with -- sized for band + layer -- is kept
+    const long long layer = balance_adjacent_max(L.bal);
+    want_full = layer >= 0 ? want_full + layer : (want_full > L.cap_full ? want_full : L.cap_full);
+  }
   L.cap_full = (int)(want_full < L.max_full ? want_full : L.max_full);
   L.cap_x = (int)(want_x < L.max_x ? want_x : L.max_x);
   return DSL_OK;
@@ -3153,6 +3230,110 @@ int dsl_slab_replan(dsl_handle* h) {
   return link_replan(h);
 }
 
+int dsl_slab_layer_counts(dsl_handle* h, float origin, int n_layers, int32_t* dev_counts) {
+  CHECK_HANDLE(h);
+  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: no slab configured");
+  if (!dev_counts) return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: null output");
+  if (n_layers < 1 || n_layers > kBalMaxLayers)
+    return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: n_layers must be between 1 and " + std::to_string(kBalMaxLayers));
+  if (!std::isfinite(origin) || !on_cell_plane(h, origin))
+    return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: origin is not on a cell plane of this handle's grid");
+  return layer_counts_on(h, origin, n_layers, dev_counts);
+}
+
+int dsl_slab_move_planes(dsl_handle* h, float lo, float hi) {
+  CHECK_HANDLE(h);
+  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: no slab configured");
+  if (!(lo < hi)) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: empty range");
+  if (h->split_pending) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: a split force pass is in flight");
+  move_planes(h, lo, hi);
+  return DSL_OK;
+}
+
+int dsl_slab_get_planes(dsl_handle* h, float* lo, float* hi) {
+  CHECK_HANDLE_ONLY(h);
+  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_get_planes: no slab configured");
+  if (lo) *lo = h->c.slab_lo;
+  if (hi) *hi = h->c.slab_hi;
+  return DSL_OK;
+}
+
+int dsl_slab_rebalance(dsl_handle* h, int every, float origin, int n_layers, const int32_t* planes, const int32_t* plane_min,
+                       const int32_t* plane_max, int min_layers) {
+  CHECK_HANDLE(h);
+  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance: call dsl_slab_attach first");
+  SlabLink& L = *h->link;
+  SlabBalance& B = L.bal;
+  if (every < 0) return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance: every must be >= 0");
+  if (every == 0) {  // off: no further look (a move the last look planned is still applied by the next step)
+    B.every = 0;
+    return DSL_OK;
+  }
+  const char* who = "dsl_slab_rebalance: ";
+  if (n_layers < 1 || n_layers > kBalMaxLayers)
+    return fail(h, DSL_ERR_INVALID, std::string(who) + "n_layers must be between 1 and " + std::to_string(kBalMaxLayers) +
+                                        " (the count's histogram), got " + std::to_string(n_layers));
+  if (min_layers < 2)
+    return fail(h, DSL_ERR_INVALID, std::string(who) + "min_layers must be >= 2 (a slab thinner than the 2h band would leave "
+                                                       "its neighbour's ghosts to two ranks), got " + std::to_string(min_layers));
+  if (!planes || !plane_min || !plane_max) return fail(h, DSL_ERR_INVALID, std::string(who) + "null planes or bounds");
+  if (!std::isfinite(origin) || !on_cell_plane(h, origin))
+    return fail(h, DSL_ERR_INVALID, std::string(who) + "origin is not on a cell plane of this handle's grid");
+  const int R = L.comm ? L.comm->nranks : 1, rank = L.comm ? L.comm->rank : 0;
+  for (int r = 0; r <= R; ++r) {
+    if (planes[r] < 0 || planes[r] > n_layers || (r > 0 && planes[r] - planes[r - 1] < min_layers))
+      return fail(h, DSL_ERR_INVALID, std::string(who) + "planes must ascend inside [0, n_layers], min_layers apart (plane " +
+                                          std::to_string(r) + ")");
+    if (r > 0 && r < R && !(plane_min[r] <= planes[r] && planes[r] <= plane_max[r]))
+      return fail(h, DSL_ERR_INVALID, std::string(who) + "plane " + std::to_string(r) + " lies outside its own bounds");
+  }
+  const int a = h->c.slab_axis;
+  const float g0 = h->c.gmin[a], g1 = h->c.gmin[a] + (float)h->c.dims[a] * h->c.cell, slack = 1.0e-3f * h->c.cell;
+  for (int side = 0; side < 2; ++side) {
+    const int r = rank + side;
+    const float cur = side == 0 ? h->c.slab_lo : h->c.slab_hi;
+    if (r == 0 || r == R) continue;  // a domain end: never moves
+    if (!(std::fabs(cur - balance_plane(h, origin, planes[r])) <= slack))
+      return fail(h, DSL_ERR_INVALID, std::string(who) + "this rank's " + (side == 0 ? "lower" : "upper") + " plane (" +
+                                          std::to_string(cur) + ") is not origin + planes[" + std::to_string(r) + "] * edge (" +
+                                          std::to_string(balance_plane(h, origin, planes[r])) + ")");
+    const float reach_lo = balance_plane(h, origin, plane_min[r]) - L.width, reach_hi = balance_plane(h, origin, plane_max[r]) + L.width;
+    if (reach_lo < g0 - slack || reach_hi > g1 + slack)
+      return fail(h, DSL_ERR_INVALID, std::string(who) + "plane " + std::to_string(r) + " with its band may reach [" +
+                                          std::to_string(reach_lo) + ", " + std::to_string(reach_hi) + "], this handle's grid covers [" +
+                                          std::to_string(g0) + ", " + std::to_string(g1) + "] along the slab axis");
+  }
+  if (!B.dev_counts)
+    if (int rc = dev_alloc(h, &B.dev_counts, (size_t)kBalMaxLayers)) return rc;
+  B.every = every;
+  B.origin = origin;
+  B.n_layers = n_layers;
+  B.min_layers = min_layers;
+  B.nranks = R;
+  B.rank = rank;
+  B.planes.assign(planes, planes + R + 1);
+  B.plane_min.assign(plane_min, plane_min + R + 1);
+  B.plane_max.assign(plane_max, plane_max + R + 1);
+  B.counts.clear();
+  B.pending = false;
+  B.looks = B.moves = 0;
+  return DSL_OK;
+}
+
+int dsl_slab_rebalance_state(dsl_handle* h, int32_t* planes, int32_t* counts, int64_t* looks, int64_t* moves) {
+  CHECK_HANDLE(h);
+  if (!h->link || h->link->bal.planes.empty())
+    return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance_state: call dsl_slab_rebalance first");
+  const SlabBalance& B = h->link->bal;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (planes) std::copy(B.planes.begin(), B.planes.end(), planes);
+  if (counts)
+    for (int k = 0; k < B.n_layers; ++k) counts[k] = B.counts.empty() ? 0 : B.counts[(size_t)k];
+  if (looks) *looks = B.looks;
+  if (moves) *moves = B.moves;
+  return DSL_OK;
+}
+
 int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
   CHECK_HANDLE(h);
   if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_wcsph_step: call dsl_slab_attach first");
@@ -3168,10 +3349,14 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
     // counting sort (drops the previous step's ghosts), densities of owned + ghosts
     if (int rc = build_grid(h, false)) return rc;
     if (int rc = density_pass(h)) return rc;
-    if (alone || !L.overlap) {
+    if (alone || !L.overlap || L.bal.pending) {
       // forces and integration of the owned particles (ghosts are marked for removal), band pack, transfer, append
       // (a rank without neighbours exchanges nothing)
       if (int rc = force_integrate(h)) return rc;
+      // re-balancing: the planes of the last look's plan take over here, where every ghost is NaN and the pack that
+      // follows hands over whoever lies outside them.  (Unsplit even with overlap: the band launch would have
+      // integrated, and would pack, the layers of the old planes.)
+      if (L.bal.pending) balance_apply(h);
       if (int rc = link_exchange(h)) return rc;
     } else {
       // band layers first; their pack and the RCCL transfer (side stream) run under the interior launch
@@ -3191,6 +3376,8 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
     }
     h->steps++;
     L.steps++;
+    if (L.bal.every > 0 && L.steps % L.bal.every == 0)
+      if (int rc = balance_look(h)) return rc;
     if (!alone && L.steps % L.replan_every == 0)
       if (int rc = link_replan(h)) return rc;
   }
@@ -3220,8 +3407,11 @@ int dsl_slab_pcisph_step(dsl_handle* h, int nsteps) {
     }
     h->pci_split_guard = false;
     if (int rc = pci_end_step(h)) return rc;  // Update; ghosts are marked for removal
+    if (L.bal.pending) balance_apply(h);      // re-balancing: as in dsl_slab_wcsph_step (migrants carry their predictor state)
     if (int rc = link_exchange(h)) return rc;
     L.steps++;
+    if (L.bal.every > 0 && L.steps % L.bal.every == 0)
+      if (int rc = balance_look(h)) return rc;
     if (!alone && L.steps % L.replan_every == 0)
       if (int rc = link_replan(h)) return rc;
   }

@@ -11,6 +11,8 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include "slab_balance.hpp"
+
 struct dsl_comm {
   ncclComm_t comm = nullptr;
   int nranks = 0, rank = 0, device = 0;
@@ -141,6 +143,55 @@ inline int xfer_all_reduce_max(dsl_handle* h, dsl_comm* c, void* words, size_t c
 
 }  // namespace
 
+// Re-balancing by moving the slab planes (dsl_slab_rebalance).  Planes are counted in cell layers from
+// `origin`; planes[r] is the plane between ranks r - 1 and r, planes[0] and planes[nranks] the domain ends.
+struct SlabBalance {
+  int every = 0;  // steps between looks; 0 = off
+  float origin = 0.f;
+  int n_layers = 0, min_layers = 2, nranks = 1, rank = 0;
+  // `planes`: the last plan -- in force, except for the move that `pending` says the next step still has to apply
+  std::vector<int32_t> planes, plane_min, plane_max;
+  std::vector<int32_t> counts;  // the last global histogram (empty before the first look)
+  bool pending = false;
+  int64_t looks = 0, moves = 0;
+  int32_t* dev_counts = nullptr;  // kBalMaxLayers words
+};
+
+// The plan: a pure integer function of values every rank holds identically (slab.plan_planes is the same rule in
+// Python; the tests hold the two equal).  Interior plane r aims at the k that minimises |S(k) R - r N| -- S the prefix
+// sum of the counts, N their total, R the number of ranks, the smallest k on a tie -- and moves ONE layer towards it,
+// unless that leaves its bounds or could leave one of the two slabs it separates thinner than min_layers: the plane
+// below has already been decided, the plane above, if it is an interior one, may itself come one layer closer.
+// Returns the number of planes that moved; `out` has R + 1 entries, the end planes are copied.
+inline int slab_plan_planes(const int32_t* counts, int n_layers, int R, const int32_t* planes, const int32_t* plane_min,
+                            const int32_t* plane_max, int min_layers, int32_t* out) {
+  for (int r = 0; r <= R; ++r) out[r] = planes[r];
+  long long N = 0;
+  for (int k = 0; k < n_layers; ++k) N += counts[k];
+  if (N == 0) return 0;
+  int moved = 0;
+  for (int r = 1; r < R; ++r) {
+    long long S = 0, best = (long long)r * N;  // k = 0: S = 0
+    int T = 0;
+    for (int k = 1; k <= n_layers; ++k) {
+      S += counts[k - 1];
+      long long d = S * R - (long long)r * N;
+      if (d < 0) d = -d;
+      if (d < best) {
+        best = d;
+        T = k;
+      }
+    }
+    const int q = planes[r] + (T > planes[r] ? 1 : (T < planes[r] ? -1 : 0));
+    if (q == planes[r] || q < plane_min[r] || q > plane_max[r]) continue;
+    const int above = planes[r + 1] - (r + 1 < R ? 1 : 0);
+    if (q - out[r - 1] < min_layers || above - q < min_layers) continue;
+    out[r] = q;
+    ++moved;
+  }
+  return moved;
+}
+
 // The slab's link to its neighbours (dsl_slab_attach): communicator, neighbour ranks, message
 // buffers, the side stream the transfer runs on.
 struct SlabLink {
@@ -160,4 +211,5 @@ struct SlabLink {
   // periodic images along the slab axis: records arriving from the lower / upper neighbour are moved by
   // these amounts (a ring closes with -L / +L at its two end ranks; 0 elsewhere)
   float shift_from_lo = 0.f, shift_from_hi = 0.f;
+  SlabBalance bal;  // dsl_slab_rebalance
 };

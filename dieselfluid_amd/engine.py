@@ -385,6 +385,39 @@ class SPHEngine:
     def slab_pcisph_step(self, nsteps: int = 1):
         self._ck(self._L.dsl_slab_pcisph_step(self._h, int(nsteps)))
 
+    # -- re-balancing: the slab planes move during a run (include/dslsph.h) -----------------------
+    def slab_layer_counts(self, origin: float, n_layers: int, dev_counts: int):
+        """owned particles per cell layer from `origin` into n_layers int32 words of device memory; asynchronous"""
+        self._ck(self._L.dsl_slab_layer_counts(self._h, C.c_float(origin), int(n_layers), C.c_void_p(dev_counts or None)))
+
+    def slab_move_planes(self, lo: float, hi: float):
+        """new [lo, hi) without touching the particles: only between an integrate and the next pack"""
+        self._ck(self._L.dsl_slab_move_planes(self._h, C.c_float(lo), C.c_float(hi)))
+
+    def slab_get_planes(self):
+        lo, hi = C.c_float(0), C.c_float(0)
+        self._ck(self._L.dsl_slab_get_planes(self._h, C.byref(lo), C.byref(hi)))
+        return float(lo.value), float(hi.value)
+
+    def slab_rebalance(self, every: int, origin: float = 0.0, n_layers: int = 0, planes=None, plane_min=None,
+                       plane_max=None, min_layers: int = 2):
+        """the native drivers look every `every` steps and move the planes (0: off); planes and bounds in layers"""
+        arr = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (planes, plane_min, plane_max)]
+        ptr = [None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32)) for a in arr]
+        self._ck(self._L.dsl_slab_rebalance(self._h, int(every), C.c_float(origin), int(n_layers), ptr[0], ptr[1], ptr[2],
+                                            int(min_layers)))
+        if every:
+            self._balance_shape = (arr[0].size, int(n_layers))  # what slab_rebalance_state has to make room for
+
+    def slab_rebalance_state(self):
+        """(planes of the last plan, last global histogram, looks, moves planned); blocking"""
+        n_planes, n_layers = getattr(self, "_balance_shape", (0, 0))
+        planes, counts = np.zeros(n_planes, dtype=np.int32), np.zeros(n_layers, dtype=np.int32)
+        looks, moves = C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.dsl_slab_rebalance_state(self._h, planes.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(looks), C.byref(moves)))
+        return planes, counts, int(looks.value), int(moves.value)
+
     def download_ids(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.int32)
         self._ck(self._L.dsl_download_ids(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size))

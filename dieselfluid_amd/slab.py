@@ -52,6 +52,33 @@ def message_counts(msg: torch.Tensor):
     return int(hdr[0]), int(hdr[1])
 
 
+def plan_planes(counts, planes, plane_min, plane_max, min_layers):
+    """The re-balancing plan (the library's slab_plan_planes, restated; the tests hold the two equal): a pure integer
+    function of the global histogram `counts` (owned particles per cell layer) and the planes in layers, so every rank
+    takes the same decision.  Interior plane r aims at the k that minimises |S(k) R - r N| (S: prefix sum, N: total, R:
+    ranks; the smallest k on a tie) and moves ONE layer towards it, unless that leaves [plane_min[r], plane_max[r]] or
+    could leave a slab next to it thinner than min_layers: the plane below has been decided, the plane above, if interior,
+    may itself come one layer closer.  The end planes never move.  Returns the new planes."""
+    counts = [int(c) for c in counts]
+    planes = [int(q) for q in planes]
+    R, out, N = len(planes) - 1, list(planes), sum(counts)
+    if N == 0:
+        return out
+    S = [0]
+    for c in counts:
+        S.append(S[-1] + c)
+    for r in range(1, R):
+        T = min(range(len(S)), key=lambda k: (abs(S[k] * R - r * N), k))
+        q = planes[r] + (1 if T > planes[r] else (-1 if T < planes[r] else 0))
+        if q == planes[r] or q < plane_min[r] or q > plane_max[r]:
+            continue
+        above = planes[r + 1] - (1 if r + 1 < R else 0)
+        if q - out[r - 1] < min_layers or above - q < min_layers:
+            continue
+        out[r] = q
+    return out
+
+
 class HipSlabEngine:
     """SPHEngine + device message buffers (torch tensors used as plain device memory)."""
 
@@ -123,6 +150,17 @@ class HipSlabEngine:
     def status(self, reset_high_water: bool = False):
         return self.eng.slab_status(reset_high_water)
 
+    # -- re-balancing: the two building blocks ------------------------------------------
+    def layer_counts(self, origin: float, n_layers: int):
+        """owned particles per cell layer, an int32 tensor on the device; asynchronous"""
+        if getattr(self, "_counts", None) is None or self._counts.numel() != n_layers:
+            self._counts = torch.zeros(n_layers, dtype=torch.int32, device=self.dev)
+        self.eng.slab_layer_counts(origin, n_layers, self._counts.data_ptr())
+        return self._counts
+
+    def move_planes(self, lo: float, hi: float):
+        self.eng.slab_move_planes(lo, hi)
+
     def nn(self):
         self.eng.nn()
 
@@ -158,8 +196,16 @@ class SlabDriver:
     REPLAN_EVERY = 8  # steps between message-size re-plans (one host sync + one tiny all-reduce)
 
     def __init__(self, engine, rank: int, world: int, axis: int, planes, width: float, width_full: float,
-                 group=None, overlap=None, margin: float = 0.0):
+                 group=None, overlap=None, margin: float = 0.0, rebalance_every: int = 0, balance=None):
+        """rebalance_every = M > 0: every M steps the ranks count their owned particles per cell layer and move the
+        planes one layer towards an even split (plan_planes).  `balance`: origin, edge (the cell edge), n_layers, and
+        planes, plane_min, plane_max in layers (world + 1 entries each), min_layers -- SlabDriver.dambreak fills it."""
         assert len(planes) == world + 1
+        assert not rebalance_every or balance is not None
+        self.rebalance_every = int(rebalance_every)
+        self.balance = None if balance is None else dict(balance, planes=[int(q) for q in balance["planes"]])
+        self.balance_log = []  # per look: (step, global histogram, planes planned)
+        self._plan_pending = False
         self.engine, self.rank, self.world, self.axis, self.group = engine, rank, world, axis, group
         self.width, self.width_full = width, width_full
         self.lo = -math.inf if rank == 0 else float(planes[rank])
@@ -233,7 +279,65 @@ class SlabDriver:
         if hw_full > max_full or hw_x > max_x:
             raise SlabOverflow(f"band occupancy ({hw_full} full, {hw_x} position-only records) outgrew the message "
                                f"buffers ({max_full}, {max_x})")
+        if self.rebalance_every > 0:
+            # a plane that moves sends one cell layer of migrants on top of the h band (as the library's re-plan does)
+            b = self.balance
+            if b.get("counts") is None:
+                want_full = max(want_full, self.engine.cap_full)
+            else:
+                adj = [b["counts"][k] for r in range(1, self.world) for k in (b["planes"][r] - 1, b["planes"][r])
+                       if 0 <= k < b["n_layers"]]
+                want_full += int(max(adj, default=0))
         self.engine.set_caps(want_full, want_x)
+
+    # -- re-balancing in the Python protocol (the native path: dsl_slab_rebalance) ------------
+    def _plane_pos(self, k: int) -> float:
+        b = self.balance
+        return float(np.float32(b["origin"]) + np.float32(k) * np.float32(b["edge"]))
+
+    def _balance_look(self):
+        """after an exchange every live particle has one owner and the planes are layer boundaries: the ranks'
+        histograms are disjoint, their MAX is their sum"""
+        b = self.balance
+        t = self.engine.layer_counts(b["origin"], b["n_layers"])
+        t = t if t.device == self.comm_dev else t.to(self.comm_dev)
+        if self.world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        counts = t.cpu().numpy().astype(np.int32)
+        new = plan_planes(counts, b["planes"], b["plane_min"], b["plane_max"], b["min_layers"])
+        self._plan_pending = self._plan_pending or new != b["planes"]
+        b["planes"], b["counts"] = new, counts
+        self.balance_log.append((self.steps, counts.copy(), list(new)))
+
+    def _balance_apply(self):
+        """between the integrate and the pack: every ghost is NaN, whoever lies outside the new planes leaves as a migrant"""
+        pl = self.balance["planes"]
+        self._plan_pending = False
+        lo = self.lo if self.rank == 0 else self._plane_pos(pl[self.rank])
+        hi = self.hi if self.rank == self.world - 1 else self._plane_pos(pl[self.rank + 1])
+        self.engine.move_planes(lo, hi)
+        self.lo, self.hi = lo, hi
+
+    def set_rebalance_every(self, every: int):
+        """0 stops the looks (a move already planned is still applied)"""
+        self.rebalance_every = int(every)
+        if getattr(self, "native", False):
+            b = self.balance
+            self.engine_core.slab_rebalance(every, b["origin"], b["n_layers"], self.balance_state()[0], b["plane_min"],
+                                            b["plane_max"], b["min_layers"])
+
+    def balance_state(self):
+        """(planes of the last plan in layers, last global histogram, looks)"""
+        if getattr(self, "native", False):
+            planes, counts, looks, _moves = self.engine_core.slab_rebalance_state()
+            return [int(q) for q in planes], counts, looks
+        b = self.balance
+        return list(b["planes"]), b.get("counts"), len(self.balance_log)
+
+    def _after_native_step(self, nsteps):
+        self.steps += nsteps
+        if self.balance is not None:
+            self.lo, self.hi = self.engine_core.slab_get_planes()
 
     # -- the exchange behind the C ABI (dsl_slab_attach & co.: RCCL inside libdslsph.so) --------
     def attach_native(self, comm=None, lo_rank=None, hi_rank=None):
@@ -259,6 +363,10 @@ class SlabDriver:
                          self.width, self.engine.cap_full, self.engine.cap_x, self.overlap)
         self.native = True
         self.native_comm = comm
+        if self.rebalance_every > 0:
+            b = self.balance
+            core.slab_rebalance(self.rebalance_every, b["origin"], b["n_layers"], b["planes"], b["plane_min"], b["plane_max"],
+                                b["min_layers"])
         return comm
 
     def wcsph_step(self, nsteps: int = 1):
@@ -267,7 +375,7 @@ class SlabDriver:
                 self.engine_core.slab_wcsph_step(nsteps)
             except DslError as e:
                 raise SlabOverflow(str(e)) if "overflow" in str(e) or "margin" in str(e) else e
-            self.steps += nsteps
+            self._after_native_step(nsteps)
             return
         e = self.engine
         lo_nb, hi_nb = self._neighbours()
@@ -279,7 +387,7 @@ class SlabDriver:
             self._ghosts_in = False
             if self.world == 1:
                 e.force_pass()
-            elif self.overlap:
+            elif self.overlap and not self._plan_pending:
                 e.force_band()       # owned particles of the cell layers near the planes
                 send = e.pack_band(self.width_full, lo_nb is not None, hi_nb is not None)
                 e.comm_stream.wait_stream(torch.cuda.current_stream(e.dev))  # ... the pack, not what follows
@@ -289,8 +397,12 @@ class SlabDriver:
                 self._finish(posted)
             else:
                 e.force_pass()       # owned only; ghosts are marked for removal
+                if self._plan_pending:   # (unsplit even with overlap: the band launch would pack the old planes' layers)
+                    self._balance_apply()
                 self.exchange()
             self.steps += 1
+            if self.rebalance_every > 0 and self.steps % self.rebalance_every == 0:
+                self._balance_look()
             if self.world > 1 and self.steps % self.REPLAN_EVERY == 0:
                 self._replan()
 
@@ -305,7 +417,7 @@ class SlabDriver:
                 self.engine_core.slab_pcisph_step(nsteps)
             except DslError as e:
                 raise SlabOverflow(str(e)) if "overflow" in str(e) or "margin" in str(e) else e
-            self.steps += nsteps
+            self._after_native_step(nsteps)
             return
         e = self.engine
         core = self.engine_core
@@ -330,8 +442,12 @@ class SlabDriver:
                     core.pcisph_error_word(self._err.data_ptr(), store=True)
                 core.pcisph_phase(2)        # convergence check
             core.pcisph_phase(3)            # Update; ghosts are marked for removal
+            if self._plan_pending:
+                self._balance_apply()       # (migrants carry their predictor state: nothing else changes)
             self.exchange()
             self.steps += 1
+            if self.rebalance_every > 0 and self.steps % self.rebalance_every == 0:
+                self._balance_look()
             if self.world > 1 and self.steps % self.REPLAN_EVERY == 0:
                 self._replan()
 
@@ -358,9 +474,17 @@ class SlabDriver:
     @classmethod
     def dambreak(cls, n3: int, math_mode: int = 1, device: int = 0, axis: int = 2, rank=None, world=None,
                  engine_factory=None, group=None, vel_fn=None, overlap=None, tile_align=True, params_hook=None,
-                 pcisph=False, native=None, **scene_kw):
+                 pcisph=False, native=None, layers=None, rebalance_every=0, rebalance_bounds=None, min_layers=2,
+                 **scene_kw):
         """Dam-break of n3^3 particles split into `world` slabs along `axis` (default z: the
-        collapse is symmetric in z, so the slabs stay balanced without re-planning)."""
+        collapse is symmetric in z, so the slabs stay balanced without re-planning).
+
+        Any other axis is not symmetric -- along x the block fills a quarter of the box -- and wants re-balancing:
+        `layers` is the initial split in LATTICE layers (world + 1 ascending entries from 0 to n3, each a whole number
+        of cells: a way to start unbalanced), `rebalance_every` = M the steps between looks (0: planes stay; the driver
+        is still set up to move them when `rebalance_bounds` is given), `rebalance_bounds` = (plane_min, plane_max),
+        world + 1 entries each, in CELL layers counted from the single-domain grid's lower face (default: anywhere
+        that leaves every slab min_layers thick), `min_layers` the thinnest slab allowed."""
         rank = dist.get_rank(group) if rank is None else rank
         world = dist.get_world_size(group) if world is None else world
         p, _ = scenes.dambreak_scene(n3, math_mode=math_mode, positions=False, **scene_kw)
@@ -377,24 +501,53 @@ class SlabDriver:
         layer = [round(r * n3 / world) for r in range(world + 1)]
         if tile_align and n3 >= 2 * per * world:
             layer = [min(n3, per * round(r * n3 / (world * per))) for r in range(world)] + [n3]
+        if layers is not None:
+            layer = [int(l) for l in layers]
+            assert len(layer) == world + 1 and layer[0] == 0 and layer[-1] == n3 and all(a < b for a, b in zip(layer, layer[1:]))
         planes = [l * dx for l in layer]
         k0, k1 = layer[rank], layer[rank + 1]
+        balance = None
+        if rebalance_every > 0 or rebalance_bounds is not None:
+            # layers of the re-balancing: the cells of the single-domain grid along the axis
+            origin0 = float(p.grid_min[axis])
+            n_layers = int(math.ceil((p.grid_max[axis] - origin0) / h - 1e-6))
+            pl = [(q - origin0) / h for q in planes]
+            assert all(abs(q - round(q)) < 1e-3 for q in pl[1:-1]), "slab planes must lie on cell planes"
+            pl = [0] + [int(round(q)) for q in pl[1:-1]] + [n_layers]
+            if rebalance_bounds is None:
+                rebalance_bounds = ([min_layers * r for r in range(world + 1)],
+                                    [n_layers - min_layers * (world - r) for r in range(world + 1)])
+            balance = dict(origin=origin0, edge=float(h), n_layers=n_layers, planes=pl, min_layers=int(min_layers),
+                           plane_min=[int(q) for q in rebalance_bounds[0]], plane_max=[int(q) for q in rebalance_bounds[1]])
         ids = scenes.dambreak_slab_ids(n3, axis, k0, k1)
         pos = scenes.dambreak_positions_ids(n3, dx, ids, scene_kw.get("jitter", 0.05), scene_kw.get("seed", 1234))
         n_local = ids.shape[0]
         width_full = h
         cap_full = int(1.25 * n3 * n3 * math.ceil(width_full / dx)) + 1024
+        if balance is not None:  # a plane that moves sends one cell layer of migrants on top of the h band
+            cap_full = int(1.25 * n3 * n3 * (math.ceil(width_full / dx) + math.ceil(h / dx))) + 1024
         cap_x = int(1.25 * n3 * n3 * math.ceil((width - width_full) / dx)) + 1024
         max_scale = 2.0
         p.n_particles = n_local
         p.capacity = int(1.25 * n_local) + int(2 * max_scale * (cap_full + cap_x)) + 1024
+        if balance is not None:  # the largest share any rank starts with: re-balancing only evens the shares out
+            share = n3 * n3 * max(b - a for a, b in zip(layer, layer[1:]))
+            p.capacity = int(1.25 * share) + int(2 * max_scale * (cap_full + cap_x)) + 1024
         # The neighbour grid only has to cover this slab plus its ghost band.  It starts a whole
         # number of 4-cell tiles below the lower plane (two empty cell layers, then the two ghost
         # layers), so tile planes coincide with the slab planes: the force pass stages no tile that
         # is half ghosts, and the band layers of the split step (the cells within width + margin =
         # 4 cells of a plane, include/dslsph.h) are whole tile layers.
         margin = 2.0 * h
-        if world > 1:
+        if world > 1 and balance is not None:
+            # the grid covers what this rank's planes may reach plus the band (and the two empty cell layers below it,
+            # as before); its origin stays on a cell plane of the single-domain grid
+            origin0 = balance["origin"]
+            if rank > 0:
+                p.grid_min[axis] = origin0 + (balance["plane_min"][rank] - 4) * h
+            if rank < world - 1:
+                p.grid_max[axis] = origin0 + (balance["plane_max"][rank + 1] + 2) * h
+        elif world > 1:
             tile = 4.0 * h
             if rank > 0:
                 gmin = planes[rank] - tile
@@ -413,7 +566,8 @@ class SlabDriver:
         if pcisph:
             eng.pcisph_begin()  # predictor state = the initial positions / velocities (pcisph_darwin.go:28-41)
             overlap = False     # the PCISPH step has no split force pass
-        drv = cls(engine, rank, world, axis, planes, width, width_full, group=group, overlap=overlap, margin=margin)
+        drv = cls(engine, rank, world, axis, planes, width, width_full, group=group, overlap=overlap, margin=margin,
+                  rebalance_every=rebalance_every, balance=balance)
         eng.slab_config(axis, drv.lo, drv.hi)
         if drv.overlap:
             engine.split(width, margin)

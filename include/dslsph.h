@@ -468,6 +468,57 @@ int dsl_slab_exchange(dsl_handle *h);
 int dsl_slab_replan(dsl_handle *h);
 int dsl_slab_wcsph_step(dsl_handle *h, int nsteps);
 int dsl_slab_pcisph_step(dsl_handle *h, int nsteps);
+/* ---- multi-GPU: re-balancing by moving the slab planes during a run (opt-in) ----
+ * A scene that is not symmetric along the slab axis leaves one rank with most of the particles.  Every M steps the
+ * ranks count their owned particles per CELL LAYER along the axis (layer k = [origin + k edge, origin + (k+1) edge),
+ * edge = the grid's cell edge, `origin` on a cell plane), sum the histograms, and every rank takes the same decision:
+ * each interior plane moves ONE layer towards the layer boundary that splits the particles evenly.  The exchange that
+ * exists carries the move: between an integrate and the pack that follows it every ghost is NaN, so ownership is purely
+ * positional; whoever lies outside the new planes is packed as a migrant, and the old owner's 2h ghost band covers the
+ * strip plus the neighbour's band for a move of up to 2h.  Off (the default) costs nothing: no kernel, no transport
+ * call, the same bits.
+ *
+ * Building blocks, for a host that runs the exchange itself:
+ * dsl_slab_layer_counts : overwrites dev_counts[0 .. n_layers) (DEVICE memory) with this handle's owned particles per
+ *                      layer; coordinates outside [origin, origin + n_layers edge) count in the first / last layer.
+ *                      Asynchronous.  DSL_ERR_INVALID without a slab, for n_layers outside [1, 4096], or if `origin`
+ *                      is not on a cell plane of this handle's grid (1e-3 cell of slack).  When every live particle
+ *                      has one owner and the planes are layer boundaries -- after an exchange -- the ranks' histograms
+ *                      are disjoint, and a MAX all-reduce of them is their sum.
+ * dsl_slab_move_planes : [lo, hi) of a configured slab changes, the particles are not touched; no host
+ *                      synchronisation (unlike dsl_slab_config).  LEGAL ONLY BETWEEN AN INTEGRATE (dsl_force_pass,
+ *                      DSL_PCI_END_STEP) AND THE NEXT dsl_slab_pack / dsl_slab_exchange, and by at most 2h per step;
+ *                      the call cannot check that.  It refuses while a split force pass is pending (the band launch
+ *                      integrated, and dsl_slab_pack_band would pack, the layers of the old planes: run that step
+ *                      unsplit) and an empty range.
+ * dsl_slab_get_planes  : the planes in force.  A host that classifies particles itself needs them once planes move.
+ *
+ * The native drivers (after dsl_slab_attach):
+ * dsl_slab_rebalance   : every = M > 0 turns it on, 0 off (a move already planned is still applied).  `planes`
+ *                      (nranks + 1 entries, in layers; [0] and [nranks] are the domain ends and never move) must be
+ *                      this run's planes -- this rank's lo / hi equal origin + planes[rank] edge and origin +
+ *                      planes[rank + 1] edge to 1e-3 cell, where they are finite --; plane r stays inside
+ *                      [plane_min[r], plane_max[r]], and no slab gets thinner than min_layers (>= 2: the 2h band must
+ *                      come from one neighbour).  [origin + plane_min edge - width, origin + plane_max edge + width]
+ *                      of this rank's two planes must lie inside this handle's grid box, n_layers <= 4096: otherwise
+ *                      DSL_ERR_INVALID, and dsl_last_error names the shortfall.  Identical arguments on every rank.
+ *                      Then dsl_slab_wcsph_step / dsl_slab_pcisph_step LOOK after the exchange of every M-th step
+ *                      (the count, ONE all_reduce_max_u32 over n_layers words, one host synchronisation, the plan) and
+ *                      APPLY a plan that moves a plane in the next step, between its integrate and its pack; that one
+ *                      step runs the unsplit exchange even with overlap = 1.  While it is on, the message re-plan adds
+ *                      the fullest layer next to an interior plane (last histogram) to the full-record capacity: attach
+ *                      with cap_full sized for the band plus one cell layer.  An undersized message or capacity remains
+ *                      DSL_ERR_OVERFLOW on every rank at the next re-plan.
+ * dsl_slab_rebalance_state : `planes` (nranks + 1): the last plan -- in force, but for a move the next step still has to
+ *                      apply; `counts` (n_layers, or NULL): the last global histogram (zeros before the first look);
+ *                      looks; plane moves planned so far.  Blocking. */
+int dsl_slab_layer_counts(dsl_handle *h, float origin, int n_layers, int32_t *dev_counts);
+int dsl_slab_move_planes(dsl_handle *h, float lo, float hi);
+int dsl_slab_get_planes(dsl_handle *h, float *lo, float *hi);
+int dsl_slab_rebalance(dsl_handle *h, int every, float origin, int n_layers, const int32_t *planes /* nranks + 1 */,
+                       const int32_t *plane_min /* nranks + 1 */, const int32_t *plane_max /* nranks + 1 */, int min_layers);
+int dsl_slab_rebalance_state(dsl_handle *h, int32_t *planes /* nranks + 1 */, int32_t *counts /* n_layers, or NULL */,
+                             int64_t *looks, int64_t *moves);
 
 /* Library options: behaviour that is the product's own and has no counterpart among the reference's parameters.
  *   DSL_OPT_SKIN (set/get): 0 = off, else a fraction s of h in (0, 0.2]; default 0.07 for DSL_MATH_FAST handles of at

@@ -9,8 +9,10 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$root/variants"
 if [ "$rev" = WORK ]; then src="$root"; else
   src=$(mktemp -d); git -C "$root" archive "$rev" dieselfluid_amd/csrc include | tar -x -C "$src"; fi
-extra=()  # (the collider's translation unit, where the revision has one)
-[ -f "$src/dieselfluid_amd/csrc/collide.hip" ] && extra=("$src/dieselfluid_amd/csrc/collide.hip")
+extra=()  # (the other translation units, where the revision has them: the collider, its cell index, the slab re-balancing count)
+for unit in collide.hip collide_index.hip slab_balance.hip; do
+  if [ -f "$src/dieselfluid_amd/csrc/$unit" ]; then extra+=("$src/dieselfluid_amd/csrc/$unit"); fi
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -std=c++17 \
   "$@" -o "$root/variants/libdslsph_$name.so" "$src/dieselfluid_amd/csrc/dslsph.hip" "${extra[@]}"
 [ "$rev" = WORK ] || rm -rf "$src"
