@@ -515,6 +515,8 @@ const (
 	OptCollideIndexEntries = int(C.DSL_OPT_COLLIDE_INDEX_ENTRIES)
 	OptCollideVisits       = int(C.DSL_OPT_COLLIDE_VISITS)
 	OptCollideFullWaves    = int(C.DSL_OPT_COLLIDE_FULL_WAVES)
+	// a collider mesh on a slab handle: every rank sets the same mesh, the slab step drivers collide after each integrate
+	OptCollideSlab = int(C.DSL_OPT_COLLIDE_SLAB)
 )
 
 // SetOption / GetOption: library options (DSL_OPT_* in include/dslsph.h), e.g. the neighbour-list skin of WCSPHStep.

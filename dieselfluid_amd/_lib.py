@@ -23,7 +23,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-ve
                "-std=c++17", "-Wall"]
 
 
-UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip", "slab_balance.hip")
+UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip", "collide_slab.hip", "slab_balance.hip")
 
 
 class DslError(RuntimeError):
@@ -177,9 +177,9 @@ def build_library(force: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise DslError("hipcc not found: cannot build libdslsph.so (no fallback exists)")
     os.makedirs(os.path.dirname(_BUILT), exist_ok=True)
-    # four translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), the cell index over
-    # its triangles with the kernel that walks it (csrc/collide_index.hip), and the slab re-balancing count
-    # (csrc/slab_balance.hip)
+    # five translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), the cell index over
+    # its triangles with the kernel that walks it (csrc/collide_index.hip), the slab forms of both collide walks
+    # (csrc/collide_slab.hip), and the slab re-balancing count (csrc/slab_balance.hip)
     cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in UNITS]
     subprocess.check_call(cmd)
     return _BUILT

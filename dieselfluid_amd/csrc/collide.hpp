@@ -1,6 +1,6 @@
 // collide.hpp -- the triangle-mesh collider's device records and the launchers of its kernels.  The kernels are compiled
 // in translation units of their own -- kernels_collide.hpp in collide.hip, kernels_collide_index.hpp in
-// collide_index.hip; dslsph.hip includes this header only.
+// collide_index.hip, the slab forms of both walks in collide_slab.hip; dslsph.hip includes this header only.
 #pragma once
 
 #include "sph_device.hpp"
@@ -92,5 +92,13 @@ int col_index_pad(int cells);  // entries of the count and start arrays for that
 // collide over the index: k_collide_indexed<respond>; m.cull is taken as 1
 void launch_collide_indexed(hipStream_t stream, bool respond, int n, float dt, Bnd bnd, ColMesh m, ColIndex ix, Soa3 p, Soa3 v,
                             ColQuery q, int* hits);
+
+// collide_slab.hip: the response pass of a slab rank (DSL_OPT_COLLIDE_SLAB).  The live count is read from c.n_ptr, so
+// the launch covers `cap` slots.  sel = 0: every live slot the last integrate wrote (a ghost's position is NaN: never
+// queried); 1: only the slots whose cell BEFORE the step, along the slab axis, is a band layer of the split step
+// (slab_band_cell on old_axis, as k_slab_count / k_slab_write decide it); 2: only the others.  A slot that is not
+// selected is not read beyond old_axis.  The walk over the cell index if `ix` is given, the list walk otherwise.
+void launch_collide_slab(hipStream_t stream, int cap, const DevConsts& c, int sel, const float* old_axis, ColMesh m,
+                         const ColIndex* ix, Soa3 p, Soa3 v, int* hits);
 
 }  // namespace dsl

@@ -1,8 +1,8 @@
 // collide_narrow.hpp -- the collider's narrow phase and its epilogue, written once: Triangle.BarycentricCollision /
 // Barycentric (geom/triangle/tri.go:37-101) for one particle against one triangle record, and what a lane does with
-// its hit (the response, or the four query returns).  Included by both collide kernels' translation units
-// (kernels_collide.hpp: the list walk; kernels_collide_index.hpp: the walk over the cell index), so that the two cannot
-// drift apart by a rounding.  The arithmetic's rules are stated at the head of kernels_collide.hpp.
+// its hit (the response, or the four query returns).  Included, through collide_walk.hpp, by every collide kernel's
+// translation unit (kernels_collide.hpp: the list walk; kernels_collide_index.hpp: the walk over the cell index;
+// collide_slab.hip: both on a slab rank), so that they cannot drift apart by a rounding.  The arithmetic's rules are stated at the head of kernels_collide.hpp.
 #pragma once
 
 #include "collide.hpp"

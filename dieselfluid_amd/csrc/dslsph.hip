@@ -187,6 +187,13 @@ struct dsl_handle {
   long long col_ix_entries = 0;
   size_t col_ix_bytes = 0;         // its share of dev_bytes
   bool col_last_indexed = false;   // the last collide pass or query ran the indexed kernel
+  // a mesh on a slab handle (DSL_OPT_COLLIDE_SLAB; csrc/collide_slab.hip).  col_stage: what the last integrate wrote and
+  // nobody has collided, packed or re-sorted since -- 0 nothing (dsl_collide_pass is refused), 1 everything (dsl_force_pass,
+  // Update), 2 the band layers into the output half (DSL_SPLIT_BAND), 3 the other layers (DSL_SPLIT_INNER).
+  // col_step_zeroed: the hit and visit counters were zeroed since the last neighbour build (they sum over a step's launches)
+  bool col_slab = false;
+  int col_stage = 0;
+  bool col_step_zeroed = false;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hpp)
   // timing
@@ -543,6 +550,8 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   if (h->lsh) return build_lsh(h);
   const int n = launch_n(h);
   h->masks_valid = false;  // slot order changes
+  h->col_stage = 0;        // (slab collider: the sort drops the NaN ghosts; nothing integrated is left to collide)
+  h->col_step_zeroed = false;
   const DevConsts& c = h->c;
   CSoa3 p = cpos(h);
   // (the histogram and the "cells to order" bitmap are clean: zeroed at creation, and again by
@@ -825,6 +834,7 @@ int force_integrate(dsl_handle* h, int part = 0) {
     }); }); });
   });
   if (rc) return rc;
+  h->col_stage = part + 1;  // (slab collider: what dsl_collide_pass may touch next)
   if (part == 1) return DSL_OK;
   h->cur_pv = o;
   h->masks_valid = false;    // positions moved
@@ -873,6 +883,7 @@ int update_pass(dsl_handle* h, bool use_xs = false) {
                        xs);
   });
   if (rc) return rc;
+  h->col_stage = 1;
   h->forces_uniform = true;
   h->press_zero = true;
   h->grid_valid = false;
@@ -1092,8 +1103,43 @@ int collide_launch(dsl_handle* h, bool respond, ColQuery q, int* hits) {
   }
   return DSL_OK;
 }
+// The pass on a slab rank (csrc/collide_slab.hip; the rules are at dsl_collide_pass in include/dslsph.h): exactly the
+// slots the last integrate wrote.  After the band launch of the split step these lie in the OUTPUT half of the state
+// and the state has not flipped; the pre-step coordinates that select band or inner slots are in the other half.
+int collide_pass_slab(dsl_handle* h) {
+  const int stage = h->col_stage;
+  if (stage == 0)
+    return fail(h, DSL_ERR_INVALID,
+                "dsl_collide_pass: on a slab handle the order is integrate -> collide -> pack / append / neighbour build, one "
+                "collide per integrate: nothing has been integrated since the last collide, dsl_slab_pack, dsl_slab_pack_band, "
+                "dsl_slab_append, dsl_slab_exchange or dsl_build_neighbours");
+  const int out = stage == 2 ? h->cur_pv ^ 1 : h->cur_pv;
+  const int sel = stage - 1;
+  const float* old_axis = sel != 0 ? h->pv[out ^ 1][h->c.slab_axis] : nullptr;
+  const bool indexed = h->col_ix_cells > 0 && h->col_cull;
+  if (!h->col_step_zeroed) {  // the counters sum over the launches of one step: band + inner
+    HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
+    if (indexed) HIP_TRY(h, hipMemsetAsync(h->col_ix.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+    h->col_step_zeroed = true;
+  }
+  h->col_last_indexed = indexed;
+  const int rc = timed(h, DSL_K_COLLIDE, [&] {
+    launch_collide_slab(h->stream, h->cap, h->c, sel, old_axis, col_mesh(h), indexed ? &h->col_ix : nullptr, mpos(h, out),
+                        mvel(h, out), h->col_hits);
+  });
+  if (rc) return rc;
+  // (a host that packs the band on a stream of its own waits for this event: it has to cover the band's collide too)
+  if (stage == 2 && h->ev_band) HIP_TRY(h, hipEventRecord(h->ev_band, h->stream));
+  h->col_stage = 0;
+  if (stage != 2) {  // (the band launch's state is still the pre-step one: its grid and masks serve the inner launch)
+    h->grid_valid = false;
+    h->masks_valid = false;
+  }
+  return DSL_OK;
+}
 int collide_pass(dsl_handle* h) {
   if (h->col_tri == 0) return DSL_OK;
+  if (h->c.n_ptr) return collide_pass_slab(h);
   HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
   int lrc = DSL_OK;
   int rc = timed(h, DSL_K_COLLIDE, [&] { lrc = collide_launch(h, true, ColQuery{}, h->col_hits); });
@@ -2117,6 +2163,12 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
       h->pci_rows_live = false;
       return DSL_OK;
     case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDE_SLAB:
+      if (value == 0.0 && h->col_slab && h->c.n_ptr && h->col_tri > 0)
+        return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_SLAB cannot go back to 0 while a slab handle holds a "
+                                        "collider mesh; remove the mesh (T = 0) or leave slab mode first");
+      h->col_slab = value != 0.0;
+      return DSL_OK;
     // the cell index over the collider's triangles: built (blocking) as soon as option, edge and mesh are all there; an
     // edge that breaks the budget is refused and leaves option, edge and index as they were
     case DSL_OPT_COLLIDE_INDEX: {
@@ -2174,6 +2226,7 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_PCI_QINCR: *value = h->pci_qincr ? 1.0 : 0.0; return DSL_OK;
     case DSL_OPT_COLLIDER_TRIANGLES: *value = (double)h->col_tri; return DSL_OK;
     case DSL_OPT_COLLIDE_CULL: *value = h->col_cull ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_COLLIDE_SLAB: *value = h->col_slab ? 1.0 : 0.0; return DSL_OK;
     case DSL_OPT_COLLIDE_HITS: {  // (blocking: the kernel counts on the device)
       int hits = 0;
       if (h->col_hits) {
@@ -2209,7 +2262,7 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
 int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* normals, size_t n_triangles, float radius,
                           float restitution) {
   CHECK_HANDLE(h);
-  if (h->c.slab_axis >= 0 || h->c.n_ptr)
+  if ((h->c.slab_axis >= 0 || h->c.n_ptr) && !h->col_slab)  // (DSL_OPT_COLLIDE_SLAB: every rank sets the same mesh)
     return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_set_mesh: a collider mesh is not supported in slab mode");
   if (n_triangles == 0) {  // removes the mesh (the arrays stay for the next one; the cell index goes)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2600,7 +2653,7 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (axis < -1 || axis > 2 || !(lo < hi)) return fail(h, DSL_ERR_INVALID, "dsl_slab_config: bad axis or empty range");
   if (h->lsh) return fail(h, DSL_ERR_UNSUPPORTED, "lsh_ref buckets are angular cones through the whole domain: no slabs");
   if (axis >= 0 && h->nb > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: boundary particles are not supported in slab mode");
-  if (axis >= 0 && h->col_tri > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
+  if (axis >= 0 && h->col_tri > 0 && !h->col_slab) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;
@@ -2707,6 +2760,7 @@ int slab_pack_on(dsl_handle* h, hipStream_t st, float width_full, float width, b
                      h->ids[h->cur_ids], dev_lo, dev_hi, cap_full, cap_x, h->pack_counts, dsl_slab_record_floats(h), pcip,
                      pciv);
   HIP_TRY(h, hipGetLastError());
+  h->col_stage = 0;  // (slab collider: a collide behind the pack would make the message stale)
   return DSL_OK;
 }
 int slab_pack_check(dsl_handle* h, const char* who, float width_full, float width, float* dev_lo, float* dev_hi,
@@ -2778,6 +2832,7 @@ static int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const 
   hipLaunchKernelGGL(k_slab_bump, dim3(1), dim3(1), 0, h->stream, dev_message_a, dev_message_b, cap_full, cap_xonly,
                      h->dn, h->cap);
   HIP_TRY(h, hipGetLastError());
+  h->col_stage = 0;  // (slab collider: the fresh ghosts are finite; a collide would move them away from their owner's state)
   h->grid_valid = false;
   h->dens_fresh = false;
   h->dens_held = false;  // (the appended records have no densities yet; the slab step's sort does not carry them)
@@ -3353,6 +3408,7 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
       // forces and integration of the owned particles (ghosts are marked for removal), band pack, transfer, append
       // (a rank without neighbours exchanges nothing)
       if (int rc = force_integrate(h)) return rc;
+      if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set) before the pack decides ownership
       // re-balancing: the planes of the last look's plan take over here, where every ghost is NaN and the pack that
       // follows hands over whoever lies outside them.  (Unsplit even with overlap: the band launch would have
       // integrated, and would pack, the layers of the old planes.)
@@ -3361,6 +3417,7 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
     } else {
       // band layers first; their pack and the RCCL transfer (side stream) run under the interior launch
       if (int rc = force_integrate(h, 1)) return rc;
+      if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set) the band layers, in the output half
       h->split_pending = true;
       if (int rc = link_pack(h, h->stream, h->split_width, true)) return rc;
       // the interior launch is queued BEHIND the pack and BEFORE the transfer is posted: the GPU goes straight from
@@ -3368,6 +3425,7 @@ int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
       HIP_TRY(h, hipEventRecord(L.ev_pack, h->stream));
       h->split_pending = false;
       if (int rc = force_integrate(h, 2)) return rc;
+      if (int rc = collide_pass(h)) return rc;  // ... the other layers: queued before the append, under the transfer
       HIP_TRY(h, hipStreamWaitEvent(L.comm_stream, L.ev_pack, 0));
       if (int rc = link_post(h, L.comm_stream)) return rc;
       HIP_TRY(h, hipEventRecord(L.ev_xfer, L.comm_stream));

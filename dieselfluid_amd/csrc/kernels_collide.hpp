@@ -14,7 +14,7 @@
 // the host layer reaches them through the launchers of collide.hpp.
 #pragma once
 
-#include "collide_narrow.hpp"  // col_dot, wave_uniform, col_narrow, col_finish: shared with kernels_collide_index.hpp
+#include "collide_walk.hpp"  // DSL_COL_WALK_LIST, and through it collide_narrow.hpp: col_dot, col_narrow, col_finish
 
 namespace dsl {
 
@@ -95,15 +95,6 @@ __global__ __launch_bounds__(64) void k_collide_chunks(int n_tri, const TriBox* 
   chunk[ch] = U;
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, kWave));
-  return wave_uniform(v);
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-  return wave_uniform(v);
-}
-
 // RESPOND: collide_narrow.hpp, col_finish.
 template <bool RESPOND>
 __global__ __launch_bounds__(kColBlock) void k_collide(int n, float dt, Bnd bnd, ColMesh m, Soa3 p, Soa3 v, ColQuery q,
@@ -119,39 +110,7 @@ __global__ __launch_bounds__(kColBlock) void k_collide(int n, float dt, Bnd bnd,
     vy = v.y[i];
     vz = v.z[i];
   }
-  // Mag(V) == 0: no collision with any triangle (tri.go:39); the root of a float is zero only for zero
-  const float mv2 = col_dot(vx, vy, vz, vx, vy, vz);
-  bool todo = live && mv2 != 0.0f;
-  // the broad phase: this wave's particles' box; off in a wave with a slow lane (0 < |V| < 1e-4, or NaN)
-  const bool slow = todo && !(mv2 >= 1.0001e-8f);
-  const bool cull = m.cull != 0 && __ballot(slow) == 0ull;
-  float wlo[3] = {0.f, 0.f, 0.f}, whi[3] = {0.f, 0.f, 0.f};
-  if (cull) {
-    const float inf = __builtin_inff();
-    wlo[0] = wave_min(todo ? px : inf);
-    wlo[1] = wave_min(todo ? py : inf);
-    wlo[2] = wave_min(todo ? pz : inf);
-    whi[0] = wave_max(todo ? px : -inf);
-    whi[1] = wave_max(todo ? py : -inf);
-    whi[2] = wave_max(todo ? pz : -inf);
-  }
-  auto skippable = [&](const TriBox& B) {
-    return B.regular != 0 && (whi[0] < B.lo[0] || wlo[0] > B.hi[0] || whi[1] < B.lo[1] || wlo[1] > B.hi[1] ||
-                              whi[2] < B.lo[2] || wlo[2] > B.hi[2]);
-  };
-
-  ColHit hit;
-  for (int cb = 0; cb < m.n_tri; cb += kColChunk) {
-    if (__ballot(todo) == 0ull) break;  // every lane has hit or stands still
-    if (cull && skippable(m.chunk[cb / kColChunk])) continue;
-    const int ce = min(cb + kColChunk, m.n_tri);
-    for (int t = cb; t < ce; ++t) {
-      if (__ballot(todo) == 0ull) break;
-      if (cull && skippable(m.box[t])) continue;
-      const TriRec R = m.rec[t];  // wave-uniform
-      if (todo && col_narrow(R, t, m.s_thr, px, py, pz, vx, vy, vz, hit)) todo = false;
-    }
-  }
+  DSL_COL_WALK_LIST(wave_min, wave_max);
 
   col_finish<RESPOND>(i, live, dt, m.rest, hit, px, py, pz, vx, vy, vz, p, v, q, hits);
 }

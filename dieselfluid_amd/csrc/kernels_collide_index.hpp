@@ -21,18 +21,12 @@
 // segment is sorted by one wave.
 #pragma once
 
-#include "collide_narrow.hpp"
+#include "collide_walk.hpp"  // col_cell, col_cell_id, DSL_COL_WALK_INDEXED
 
 namespace dsl {
 
 constexpr int kColScanPer = 8;                     // cells per lane and trip of k_index_scan
 constexpr int kColScanTrip = kWave * kColScanPer;  // the count and start arrays are padded to a multiple of this
-
-// THE cell coordinate, of a box corner and of a particle alike; monotone in x.  For origin <= x <= top.
-__device__ __forceinline__ int col_cell(float x, float origin, float edge, int dim) {
-  const float f = floorf((x - origin) / edge);
-  return (int)fminf(fmaxf(f, 0.0f), (float)(dim - 1));
-}
 
 struct ColRange {
   int lo[3], hi[3];
@@ -45,10 +39,6 @@ __device__ __forceinline__ ColRange col_range(const TriBox& B, const ColIndex& i
   }
   return r;
 }
-__device__ __forceinline__ int col_cell_id(int cx, int cy, int cz, const ColIndex& ix) {
-  return (cz * ix.dims[1] + cy) * ix.dims[0] + cx;
-}
-
 // kColBoundsWaves waves of one workgroup each: wave w takes triangles w * 64 + lane, + 64 * kColBoundsWaves, ...
 __global__ __launch_bounds__(kWave) void k_index_bounds(int n_tri, const TriBox* __restrict__ box, ColBounds* __restrict__ out) {
   const float inf = __builtin_inff();
@@ -202,19 +192,6 @@ __global__ __launch_bounds__(kWave) void k_index_always(int n_tri, const TriBox*
   }
 }
 
-// The wave-wide minimum as a scalar.  Every lane of the wave must be active (the callers' control flow is wave-uniform
-// and the kernel has no early return).  Four steps inside each row of 16 lanes, the rows combined by the two row
-// broadcasts, lane 63 holds the result.
-__device__ __forceinline__ int wave_min_i32(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));   // quad_perm:[1,0,3,2]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));   // quad_perm:[2,3,0,1]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));  // row_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false));  // row_bcast:15 into rows 1 and 3
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false));  // row_bcast:31 into rows 2 and 3
-  return __builtin_amdgcn_readlane(v, kWave - 1);
-}
-
 // k_collide over the index.  One lane per particle slot; a lane that moves and lies inside the grid holds a cursor into
 // its cell's list and a window of up to eight entries of it (two aligned 16-byte loads, the second in flight while the
 // first is used), the wave a cursor into the always-list.  The next triangle is the minimum of the heads; lanes whose
@@ -234,73 +211,7 @@ __global__ __launch_bounds__(kColBlock) void k_collide_indexed(int n, float dt, 
     vy = v.y[i];
     vz = v.z[i];
   }
-  const float mv2 = col_dot(vx, vy, vz, vx, vy, vz);
-  bool todo = live && mv2 != 0.0f;  // Mag(V) == 0: no collision with any triangle (tri.go:39)
-  const bool slow = todo && !(mv2 >= 1.0001e-8f);
-  const bool full = __ballot(slow) != 0ull;
-
-  ColHit hit;
-  int visits = 0;
-  if (full) {
-    for (int t = 0; t < m.n_tri; ++t) {
-      if (__ballot(todo) == 0ull) break;
-      const TriRec R = m.rec[t];  // wave-uniform
-      ++visits;
-      if (todo && col_narrow(R, t, m.s_thr, px, py, pz, vx, vy, vz, hit)) todo = false;
-    }
-  } else {
-    int cur = 0, end = 0;
-    if (todo && px >= ix.origin[0] && px <= ix.top[0] && py >= ix.origin[1] && py <= ix.top[1] && pz >= ix.origin[2] &&
-        pz <= ix.top[2]) {
-      const int c = col_cell_id(col_cell(px, ix.origin[0], ix.edge, ix.dims[0]), col_cell(py, ix.origin[1], ix.edge, ix.dims[1]),
-                                col_cell(pz, ix.origin[2], ix.edge, ix.dims[2]), ix);
-      cur = ix.start[c];
-      end = ix.start[c + 1];
-    }
-    const int4* __restrict__ list4 = reinterpret_cast<const int4*>(ix.list);
-    const int4 none4 = make_int4(kColNone, kColNone, kColNone, kColNone);
-    int4 w = none4, nw = none4;
-    if (cur < end) {
-      w = list4[cur >> 2];
-      cur += 4;
-    }
-    if (cur < end) {
-      nw = list4[cur >> 2];
-      cur += 4;
-    }
-    int ai = 0;
-    int a = ix.n_always > 0 ? ix.always[0] : kColNone;  // wave-uniform, like everything about the always-list
-    for (;;) {
-      if (__ballot(todo) == 0ull) break;  // every lane has hit or stands still: the always-list is nobody's business either
-      const int t = min(wave_min_i32(todo ? w.x : kColNone), a);  // a scalar
-      if (t == kColNone) break;
-      if (t == a) {
-        ++ai;
-        a = ai < ix.n_always ? ix.always[ai] : kColNone;
-      }
-      const TriRec R = m.rec[t];  // wave-uniform: one 16-dword scalar load
-      ++visits;
-      if (todo && col_narrow(R, t, m.s_thr, px, py, pz, vx, vy, vz, hit)) todo = false;
-      if (w.x == t) {
-        w.x = w.y;
-        w.y = w.z;
-        w.z = w.w;
-        w.w = kColNone;
-        if (w.x == kColNone) {  // (the fill of a segment's last window: the list is at its end as well)
-          w = nw;
-          nw = none4;
-          if (cur < end) {
-            nw = list4[cur >> 2];
-            cur += 4;
-          }
-        }
-      }
-    }
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    if (visits) atomicAdd(&ix.counters[0], (unsigned long long)visits);
-    if (full) atomicAdd(&ix.counters[1], 1ull);
-  }
+  DSL_COL_WALK_INDEXED();
   col_finish<RESPOND>(i, live, dt, m.rest, hit, px, py, pz, vx, vy, vz, p, v, q, hits);
 }
 

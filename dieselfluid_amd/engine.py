@@ -544,7 +544,7 @@ class SPHEngine:
                "pci_qpair": 21, "pci_qrows": 22, "pci_qincr": 23, "list_build": 24, "grid_oversub": 25, "tile_queue": 26,
                "collider_triangles": 32, "collide_hits": 33, "collide_cull": 34,
                "collide_index": 35, "collide_index_edge": 36, "collide_index_cells": 37, "collide_index_entries": 38,
-               "collide_visits": 39, "collide_full_waves": 40}
+               "collide_visits": 39, "collide_full_waves": 40, "collide_slab": 41}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

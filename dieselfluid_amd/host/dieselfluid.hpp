@@ -302,7 +302,8 @@ class SPH {
   // The collider list of sph.Init (fluid.go:28,41) handed to the device: the meshes' triangles and normals concatenated in
   // list order (Mesh.Collision per mesh in list order is Mesh.Collision of the concatenation), queried with radius r;
   // `e` is the build-defined response's restitution.  An empty list removes the collider.  From then on the step
-  // drivers run the collide pass after Update (include/dslsph.h: dsl_collider_set_mesh).
+  // drivers run the collide pass after Update (include/dslsph.h: dsl_collider_set_mesh).  (A slab handle takes a mesh
+  // only with DSL_OPT_COLLIDE_SLAB = 1, set through dsl_set_option on handle(); this single-domain mirror never needs it.)
   void Colliders(const std::vector<mesh::Mesh*>& meshes, float r, float e) {
     std::vector<float> verts, normals;
     for (const mesh::Mesh* m : meshes) {

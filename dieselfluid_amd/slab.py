@@ -170,6 +170,17 @@ class HipSlabEngine:
     def force_pass(self):
         self.eng.force_pass()
 
+    # -- a collider mesh on a slab rank (DSL_OPT_COLLIDE_SLAB) ------------------------------
+    def set_collider(self, vertices, normals, radius: float, restitution: float):
+        """the same mesh on every rank (the library cannot check that); switches the option on"""
+        self.eng.set_option("collide_slab", 1)
+        self.eng.set_collider_mesh(vertices, normals, radius, restitution)
+
+    def collide(self):
+        """exactly what the last integrate wrote: after force_pass everything, after force_band the band layers (before
+        pack_band), after force_inner the others (before the append)"""
+        self.eng.collide()
+
     def owned_state(self, axis, lo, hi):
         """Particles this rank is responsible for: finite positions inside [lo,hi).  After a
         step the old ghosts carry NaN, the freshly received ones and the particles that have
@@ -214,6 +225,7 @@ class SlabDriver:
         self.comm_dev = torch.device("cpu") if self.backend != "nccl" else getattr(engine, "dev", torch.device("cuda"))
         self.overlap = bool(getattr(engine, "supports_split", False) and world > 1) if overlap is None else overlap
         self.margin = margin
+        self.collider = False  # a mesh is set on every rank (dambreak(collider=...)): the protocol collides after each integrate
         self.steps = 0
         self._recv = None
         self._ghosts_in = False  # the ghosts for the next step are already appended
@@ -387,16 +399,24 @@ class SlabDriver:
             self._ghosts_in = False
             if self.world == 1:
                 e.force_pass()
+                if self.collider:
+                    e.collide()
             elif self.overlap and not self._plan_pending:
                 e.force_band()       # owned particles of the cell layers near the planes
+                if self.collider:
+                    e.collide()      # ... before their pack: the message carries the response
                 send = e.pack_band(self.width_full, lo_nb is not None, hi_nb is not None)
                 e.comm_stream.wait_stream(torch.cuda.current_stream(e.dev))  # ... the pack, not what follows
                 with torch.cuda.stream(e.comm_stream):
                     posted = self._post(send)
                 e.force_inner()      # the rest, concurrently with the transfer
+                if self.collider:
+                    e.collide()      # the other layers only; queued before the append
                 self._finish(posted)
             else:
                 e.force_pass()       # owned only; ghosts are marked for removal
+                if self.collider:
+                    e.collide()      # before the pack decides who owns a particle the response set back across a plane
                 if self._plan_pending:   # (unsplit even with overlap: the band launch would pack the old planes' layers)
                     self._balance_apply()
                 self.exchange()
@@ -441,7 +461,7 @@ class SlabDriver:
                         self._err.copy_(t)
                     core.pcisph_error_word(self._err.data_ptr(), store=True)
                 core.pcisph_phase(2)        # convergence check
-            core.pcisph_phase(3)            # Update; ghosts are marked for removal
+            core.pcisph_phase(3)            # Update; ghosts are marked for removal (and the collide pass, while a mesh is set)
             if self._plan_pending:
                 self._balance_apply()       # (migrants carry their predictor state: nothing else changes)
             self.exchange()
@@ -475,7 +495,7 @@ class SlabDriver:
     def dambreak(cls, n3: int, math_mode: int = 1, device: int = 0, axis: int = 2, rank=None, world=None,
                  engine_factory=None, group=None, vel_fn=None, overlap=None, tile_align=True, params_hook=None,
                  pcisph=False, native=None, layers=None, rebalance_every=0, rebalance_bounds=None, min_layers=2,
-                 **scene_kw):
+                 collider=None, collide_index=False, **scene_kw):
         """Dam-break of n3^3 particles split into `world` slabs along `axis` (default z: the
         collapse is symmetric in z, so the slabs stay balanced without re-planning).
 
@@ -484,7 +504,10 @@ class SlabDriver:
         of cells: a way to start unbalanced), `rebalance_every` = M the steps between looks (0: planes stay; the driver
         is still set up to move them when `rebalance_bounds` is given), `rebalance_bounds` = (plane_min, plane_max),
         world + 1 entries each, in CELL layers counted from the single-domain grid's lower face (default: anywhere
-        that leaves every slab min_layers thick), `min_layers` the thinnest slab allowed."""
+        that leaves every slab min_layers thick), `min_layers` the thinnest slab allowed.
+
+        `collider` = (vertices, normals, radius, restitution): a triangle mesh, set on every rank (the mesh is replicated;
+        DSL_OPT_COLLIDE_SLAB); `collide_index` builds the cell index over its triangles on every rank."""
         rank = dist.get_rank(group) if rank is None else rank
         world = dist.get_world_size(group) if world is None else world
         p, _ = scenes.dambreak_scene(n3, math_mode=math_mode, positions=False, **scene_kw)
@@ -563,6 +586,10 @@ class SlabDriver:
             eng.upload("velocities", np.ascontiguousarray(vel_fn(ids, pos), dtype=np.float32))
         eng.set_ids(ids)
         eng.reset_forces()
+        if collider is not None:
+            if collide_index:
+                eng.set_option("collide_index", 1)
+            engine.set_collider(*collider)
         if pcisph:
             eng.pcisph_begin()  # predictor state = the initial positions / velocities (pcisph_darwin.go:28-41)
             overlap = False     # the PCISPH step has no split force pass
@@ -571,6 +598,7 @@ class SlabDriver:
         eng.slab_config(axis, drv.lo, drv.hi)
         if drv.overlap:
             engine.split(width, margin)
+        drv.collider = collider is not None
         drv.params = p
         drv.n_total = n3 ** 3
         # real GPUs, one per rank: the library drives the step, RCCL included.  (gloo rehearsals and the

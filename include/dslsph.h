@@ -292,15 +292,46 @@ int dsl_pcisph_get_binning(dsl_handle *h, int *mode, int *active, int *escaped);
  * Response (build-defined, like the wall box): a colliding particle with k = ((a - P).n) / (n.V) >= 0 -- the plane lies
  * ahead along V -- is set back to `point` and v <- v - n * ((1 + restitution) * (v.n)); a receding one (k < 0) is left
  * alone.  Boundary particles are not queried; the PCISPH predictor state is not touched.
- * dsl_collider_set_mesh : T = 0 removes the mesh.  Blocking.  Not available in slab mode (DSL_ERR_UNSUPPORTED).  A call
- *                         refused for its arguments leaves the mesh that was set; one that fails on the device
- *                         (DSL_ERR_NOMEM, DSL_ERR_DEVICE) leaves the handle without a mesh.
+ * dsl_collider_set_mesh : T = 0 removes the mesh.  Blocking.  Not available in slab mode (DSL_ERR_UNSUPPORTED) unless
+ *                         DSL_OPT_COLLIDE_SLAB is 1 (below).  A call refused for its arguments leaves the mesh that was
+ *                         set; one that fails on the device (DSL_ERR_NOMEM, DSL_ERR_DEVICE) leaves the handle without a mesh.
  * dsl_collide_pass      : query + response for every fluid particle.  Asynchronous.  Without a mesh: nothing.
- * dsl_collider_query    : the four returns in host order, no response; any pointer may be NULL.  Blocking.
+ * dsl_collider_query    : the four returns in host order, no response; any pointer may be NULL.  Blocking.  Not
+ *                         available in slab mode, with or without DSL_OPT_COLLIDE_SLAB: its results are in host order,
+ *                         which a rank does not have.
  * While a mesh is set the step drivers run the collide pass after Update: dsl_wcsph_step after force + integrate,
  * dsl_pcisph_step and DSL_PCI_END_STEP after Update (dsl_update_pass and dsl_force_pass stay one to one), the skin step
  * is not taken, and dsl_stats.max_vel / max_f stay what Update saw.  Without a mesh no kernel is launched and no result
- * changes by a bit. */
+ * changes by a bit.
+ *
+ * Slab ranks (DSL_OPT_COLLIDE_SLAB = 1; with 0, the default, a slab handle refuses a mesh and a handle with a mesh refuses
+ * dsl_slab_config, both DSL_ERR_UNSUPPORTED).  The mesh is REPLICATED: every rank sets the same triangles, radius and
+ * restitution.  The library cannot check that the ranks agree -- a rank sees its own handle only; ranks that disagree
+ * compute different flows on the two sides of a plane.  A collision needs no neighbour (the query reads one particle
+ * and the mesh), so what a rank adds is bookkeeping: dsl_collide_pass on a slab handle collides exactly the particles
+ * the LAST INTEGRATE on this handle wrote, and nothing else --
+ *   after dsl_force_pass, dsl_update_pass or DSL_PCI_END_STEP : every live slot whose position is not NaN.  (The
+ *       integrate marked the ghosts NaN: they are never queried or counted, never widen a wave's broad-phase box and
+ *       never make a wave walk the whole list.  A ghost needs no collision of its own: its owner collides it before the
+ *       pack that sends it.)
+ *   after dsl_force_pass_split(DSL_SPLIT_BAND)  : on the OUTPUT half of the state, where dsl_slab_pack_band reads, the
+ *       slots whose cell before the step is a band layer -- the rule the band pack applies.
+ *   after dsl_force_pass_split(DSL_SPLIT_INNER) : the slots of the other layers only; a band particle is already in a
+ *       message and is not collided a second time.
+ * The order is integrate -> collide -> pack / append / neighbour build.  DSL_ERR_INVALID (the text names that order): a
+ * second collide without an integrate in between; a collide after dsl_slab_pack, dsl_slab_pack_band (for that phase),
+ * dsl_slab_append*, dsl_slab_exchange or dsl_build_neighbours -- after an append the fresh ghosts are finite and would
+ * be moved away from their owner's state, after a pack the message would be stale.  A particle that crossed a plane in
+ * the integrate and is set back across it by the response is not a migrant: ownership is decided by the pack.
+ * DSL_OPT_COLLIDE_HITS / _VISITS / _FULL_WAVES hold the sum over the launches of one step (split step: band + inner;
+ * zeroed by the first pass after a neighbour build); DSL_K_COLLIDE times each launch.  dsl_stats.max_vel / max_f, the
+ * PCISPH predictor state and the split step's margin test are what they are without the pass.  Boundary particles stay
+ * refused in slab mode.
+ * The native slab drivers run the pass directly after each integrate and before the pack that follows it, while a mesh
+ * is set: unsplit integrate -> collide -> (planes move) -> exchange; split band integrate -> band collide -> band pack,
+ * inner integrate -> inner collide -> append (the transfer still runs under the inner launches); PCISPH in
+ * DSL_PCI_END_STEP, as on a single domain.  Without a mesh: the launches, transport calls and bits of a library that
+ * has no such option. */
 int dsl_collider_set_mesh(dsl_handle *h, const float *vertices /* 9*T */, const float *normals /* 3*T */,
                           size_t n_triangles, float radius, float restitution);
 int dsl_collide_pass(dsl_handle *h);
@@ -424,6 +455,8 @@ int dsl_get_count(dsl_handle *h, int *n_live, int *n_owned); /* blocking */
  *                      step at the end of each step (with overlap: band layers first, their pack and
  *                      the transfer on a side stream under the interior force launch); PCISPH adds
  *                      one 4-byte MAX all-reduce of the iteration error per correction iteration.
+ *                      While a collider mesh is set (DSL_OPT_COLLIDE_SLAB) the collide pass follows every
+ *                      integrate and precedes the pack behind it (see dsl_collide_pass).
  *                      Every 8th step the band high-water marks of all ranks are MAX-reduced (one
  *                      host synchronisation) and every rank switches to the same new message
  *                      sizes; an overflow or an outrun split margin ANYWHERE makes the call fail with
@@ -591,7 +624,10 @@ enum {
   DSL_OPT_COLLIDE_INDEX_ENTRIES = 38, /* (get) cell-list entries plus always-list entries (the irregular triangles) */
   DSL_OPT_COLLIDE_VISITS = 39,        /* (get, blocking) triangle records loaded, summed over the waves of the last collide pass or
                                          query that the indexed kernel ran (full-walk waves included); -1: the list walk ran it */
-  DSL_OPT_COLLIDE_FULL_WAVES = 40     /* (get, blocking) waves of that launch that walked the whole list (a slow lane); -1 likewise */
+  DSL_OPT_COLLIDE_FULL_WAVES = 40,    /* (get, blocking) waves of that launch that walked the whole list (a slow lane); -1 likewise */
+  DSL_OPT_COLLIDE_SLAB = 41           /* (set/get, default 0) 1: a collider mesh on a slab handle -- dsl_collider_set_mesh and
+                                         dsl_slab_config accept each other, in either order; the rules are at dsl_collide_pass.
+                                         Back to 0 while a slab handle holds a mesh: DSL_ERR_INVALID, nothing changes */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
