@@ -23,7 +23,12 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-ve
                "-std=c++17", "-Wall"]
 
 
-UNITS = ("dslsph.hip", "collide.hip", "collide_index.hip", "collide_slab.hip", "slab_balance.hip")
+def _sources():
+    return sorted(os.path.join(_SRC_DIR, f) for f in os.listdir(_SRC_DIR) if f.endswith((".hip", ".hpp")))
+
+
+# the library's translation units: every *.hip of csrc/ (host/Makefile and tools/build_variant.sh take the same listing)
+UNITS = tuple(os.path.basename(f) for f in _sources() if f.endswith(".hip"))
 
 
 class DslError(RuntimeError):
@@ -164,10 +169,6 @@ def library_path() -> str:
     return _LIB
 
 
-def _sources():
-    return sorted(os.path.join(_SRC_DIR, f) for f in os.listdir(_SRC_DIR) if f.endswith((".hip", ".hpp")))
-
-
 def build_library(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 ... -> dieselfluid_amd/lib/libdslsph.so (in-tree)."""
     deps = _sources() + [_HDR]
@@ -177,10 +178,9 @@ def build_library(force: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise DslError("hipcc not found: cannot build libdslsph.so (no fallback exists)")
     os.makedirs(os.path.dirname(_BUILT), exist_ok=True)
-    # five translation units: the engine, the triangle-mesh collider's kernels (csrc/collide.hip), the cell index over
-    # its triangles with the kernel that walks it (csrc/collide_index.hip), the slab forms of both collide walks
-    # (csrc/collide_slab.hip), and the slab re-balancing count (csrc/slab_balance.hip)
-    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [os.path.join(_SRC_DIR, f) for f in UNITS]
+    # one command over every unit (DESIGN.md 1 has the map: the engine with all its kernels, the host-only collider and
+    # slab-link units, and the small kernel units of the collider and the slab re-balancing count)
+    cmd = [hipcc] + HIPCC_FLAGS + ["-o", _BUILT] + [d for d in deps if d.endswith(".hip")]
     subprocess.check_call(cmd)
     return _BUILT
 

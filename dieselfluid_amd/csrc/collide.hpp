@@ -1,6 +1,6 @@
 // collide.hpp -- the triangle-mesh collider's device records and the launchers of its kernels.  The kernels are compiled
 // in translation units of their own -- kernels_collide.hpp in collide.hip, kernels_collide_index.hpp in
-// collide_index.hip, the slab forms of both walks in collide_slab.hip; dslsph.hip includes this header only.
+// collide_index.hip, the slab forms of both walks in collide_slab.hip; the host units (engine.hpp) include this header only.
 #pragma once
 
 #include "sph_device.hpp"

@@ -31,9 +31,7 @@
 #include "kernels_lsh.hpp"
 #include "kernels_tiled.hpp"
 #include "kernels_skin.hpp"
-#include "collide.hpp"
-
-struct SlabLink;
+#include "engine.hpp"  // the handle and what the other host units (collider_host.hip, slab_link.hip) share with this one
 
 using namespace dsl;
 
@@ -41,205 +39,25 @@ namespace {
 std::string g_create_error;
 }
 
-// DSL_OPT_SKIN of a DSL_MATH_FAST handle ...  (0.08: measured best of 0.06 .. 0.10 on the 16M lattice -- 9234 / 9387 /
-// 9288 M particle-steps/s, profiles/r04 -- and a tile of 4 x 4 x 3 such cells stays a fifth below the LDS image's kTCap
-// records where 0.10 sits at its edge: at 0.11 the lattice's fullest tiles no longer fit and the step takes 3.4 ms)
-constexpr float kSkinDefault = 0.07f;  // (0.08 before the lists were built at predicted positions: profiles/r04_skin_sweep_predict.jsonl)
-// the lists are built where the particles will be about half way through the lists' life: the fastest particle may use up
-// this fraction of the displacement budget at the build itself (DSL_OPT_SKIN_PREDICT; 0: built where the particles are)
-constexpr float kSkinPredict = 0.8f;
-constexpr int kSkinDefaultParticles = 200000;  // ... of at least this many particles (measured: +24 % at 262k, +21 % at 1M, +15 % at 2M, +19 % at 16M)
-
-struct dsl_handle {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  dsl_params prm{};
-  DevConsts c{};
-  int n = 0, cap = 0, ncell = 0, ncell_pad = 0, nscan = 0;
-  // boundary particles (particle_array.go:123-128): ids n_fluid .. n-1.  The reference's Get() reads
-  // index == N() as the zero particle (particle_array.go:98,107), so the first boundary particle takes
-  // part in every sum AT THE ORIGIN; the device copy holds (0,0,0) for it and b0_pos what was uploaded.
-  int nb = 0;  // boundary particles; N() = n - nb (n itself changes in slab mode, where nb is always 0)
-  float b0_pos[3] = {0.f, 0.f, 0.f};
-  bool ids_global = false;  // dsl_set_ids replaced the host-order map
-  int* dcounter = nullptr;
-  // slab mode: [0] live particle count, [1..4] band counters (lo/hi full, lo/hi position-only),
-  // [5] overflow high-water mark, [6],[7] largest full / position-only band counts seen
-  int* dn = nullptr;
-  int* pack_counts = nullptr;  // band selection: per-block record counts, then offsets (kernels_grid.hpp)
-  // split slab step (dsl_force_pass_split): band tiles first, interior tiles after the pack
-  float split_margin = 0.0f, split_width = 0.0f;
-  bool split_pending = false;
-  bool pci_split_guard = false;  // between DSL_PCI_BEGIN_STEP and DSL_PCI_END_STEP
-  hipEvent_t ev_band = nullptr;
-  // DSL_NEIGH_LSH_REF
-  bool lsh = false;
-  int lsh_bits = 0, lsh_cap = 0;
-  float* hashv = nullptr;
-  int *bucket_of = nullptr, *lsh_table = nullptr, *lsh_len = nullptr, *lsh_samples = nullptr;
-  TileGrid tg{};
-  int *tiles = nullptr, *n_tiles = nullptr;
-  int *tile_desc_of = nullptr, *tile_desc = nullptr;  // per list entry: index of the tile's table; the tables (k_tile_desc)
-  // SoA state
-  float* pv[2][6] = {};
-  int* ids[2] = {};
-  float* frc[2][3] = {};
-  float* pci[2][6] = {};
-  float *rho = nullptr, *pterm = nullptr, *press = nullptr, *scratch1 = nullptr;
-  float* gterm[3] = {};  // PCISPH: cached pressure-gradient force term
-  // PCISPH with the DensityF query points in bins of their own (kernels_sph.hpp: k_pci_predict_bin): the histogram over
-  // the particles' grid cells, its prefix, the scan's tile sums, one record per query, and the 512 drift counters the
-  // un-binned kernels keep.  pci_bin_mode: 0 = the library switches when 0.2 % of the predicted positions have left their
-  // particle's tile (looked at every kPciDriftPeriod steps; a one-way latch until the next dsl_pcisph_begin), 1 = always,
-  // -1 = never (dsl_pcisph_set_binning; DSL_PCI_BINNED presets it)
-  int pci_bin_mode = 0;
-  int build_seq = 0;  // neighbour builds so far (k_cell_rank<true> stamps its off-grid flag with it)
-  // the query histogram was handed to an iteration that may not have cleaned it again (the table builder / the scan do,
-  // behind the predictor: an error return in between leaves it dirty -- the sort's sort_scratch_dirty, for the queries)
-  bool qcount_dirty = false;
-  bool pci_counters_clean = false;  // n_qtiles[0..1] are known to be zero (the first binned iteration clears them itself)
-  bool pci_iter_pending = false;  // DSL_PCI_ITERATE without its DSL_PCI_CHECK yet (the check clears the iteration's counters)
-  bool pci_binned = false;
-  bool pci_qpair = true;   // ... two queries per lane (DSL_PCI_QPAIR=0: one)
-  bool pci_qtiled = true;  // FAST: sweep the binned queries tile by tile out of LDS (DSL_PCI_QTILED=0: the global-memory sweep)
-  int64_t pci_steps = 0;  // completed steps since dsl_pcisph_begin
-  int *qcount = nullptr, *qstart = nullptr, *qsums = nullptr;
-  int *qtiles = nullptr, *n_qtiles = nullptr, *qtile_desc = nullptr;  // FAST: the tiles that hold queries and their tables
-  // FAST, two queries per lane: kQueryRow record slots per grid cell instead of the sorted array (no prefix scan, no
-  // scatter pass: kernels_tiled.hpp, tile_setup_load_counts); DSL_PCI_QROWS=0, or an allocation that fails, keeps the array
-  float4* qrows = nullptr;
-  bool pci_qrows = true;
-  // ... and the rows kept from one correction iteration to the next inside a step (k_pci_predict_bin<.., INCR>): qslot =
-  // every particle's record index; pci_rows_live = this step's rows hold every query (its first iteration filled them)
-  int* qslot = nullptr;
-  bool pci_qincr = true;
-  bool pci_rows_live = false;
-  float4* qrec = nullptr;
-  unsigned int* pci_drift = nullptr;
-  unsigned int* pci_drift_host = nullptr;  // pinned: the snapshot of the counters the next look reads
-  hipEvent_t ev_drift = nullptr;
-  bool drift_pending = false;
-  float* xsph[3] = {};   // build-defined XSPH correction of the current step (PCISPH path)
-  unsigned int* nmask = nullptr;  // FAST: per-particle in-range masks from the density sweep (kMaskWords x cap)
-  bool masks_valid = false;
-  int *rank = nullptr, *cell_count = nullptr, *cell_start = nullptr, *block_sums = nullptr;
-  // in-cell ordering of the counting sort (kernels_grid.hpp, k_scatter): bitmap of the cells to order,
-  // their ids at the slots the atomic ranks name, one byte per particle that marks their particles
-  unsigned int* unordered = nullptr;
-  int *sort_keys = nullptr, *sort_work = nullptr;
-  int* cell_keys = nullptr;  // kCellKeys ids per grid cell: the one-pass in-cell ordering (kernels_grid.hpp); DSL_OPT_CELL_KEYS = 0: nullptr
-  int* cell_keys_alloc = nullptr;
-  float* stage = nullptr;
-  DevStats* dstats = nullptr;
-  int cur_pv = 0, cur_ids = 0, cur_f = 0, cur_pci = 0;
-  bool grid_valid = false, forces_uniform = false, press_zero = true, pci_active = false, dens_fresh = false;
-  // dens_held: rho / pterm hold per-particle values in the CURRENT slot order (possibly stale ones: after a mass
-  // change or new boundary particles the reference, too, keeps the old density on the same particle until the
-  // next DensityAll), so a sort has to carry them.  dens_fresh: they also belong to the current positions / mass.
-  bool dens_held = false;
-  // the histogram / "cells to order" bitmap were handed to a build that may not have cleaned them again
-  bool sort_scratch_dirty = false;
-  // (a one-launch decoupled look-back scan was measured in round 3: 6 x SLOWER at 16.4M cells, 0.46 against 0.077 ms --
-  // all 4004 tiles are resident at once, so the look-back is one long chain of agent-scope round trips through the
-  // eight XCDs' separate L2s; profiles/README.md, r03.  Removed in round 4.)
-  bool density_pair = true;  // FAST density with two targets per lane (DSL_DENSITY_PAIR=0: the lane-per-target kernel)
-  int max_persistent_blocks = 0;  // DSL_PERSISTENT_BLOCKS (tests)
-  int64_t steps = 0;
-  size_t dev_bytes = 0;  // device memory this handle has allocated (DSL_OPT_DEVICE_BYTES)
-  // the skin step (kernels_skin.hpp; DSL_OPT_SKIN): neighbour lists against h (1 + skin), walked until some particle may
-  // have moved skin * h / 2.  skin_live: the device's SkinState is the authority on which slot -> particle map is current
-  // and the grid's cells are h (1 + skin) wide -- every other entry point settles that first (skin_settle).
-  float skin = 0.0f;
-  bool skin_live = false;
-  int64_t skin_steps_total = 0, skin_rebuilds_total = 0;  // of the skin episodes already settled
-  bool skin_list_overflow = false;
-  // the flow outran the skin (SkinState::give_up, looked at every kSkinLook steps): plain steps until step skin_retry_at
-  int64_t skin_retry_at = 0, skin_live_steps = 0;
-  int skin_suspensions = 0;
-  int tile_box[3] = {8, 4, 4};
-  int alloc_ntiles = 0;  // tiles the tile lists and tables were allocated for
-  int tile_tbz = kTB;  // cell layers per tile along z (kernels_tiled.hpp: TileGrid::tbz); 3 while the skin step owns the grid
-  SkinState* skin_state = nullptr;
-  uint4* lists = nullptr;
-  float* pvz[6] = {};  // the sort's output set of a skin step (Z)
-  float* pvr[3] = {};  // ... and the build's reference positions x + tau v in the same order (SkinState::tau)
-  float skin_predict = kSkinPredict;  // DSL_OPT_SKIN_PREDICT
-  bool list_build_lockstep = true;    // DSL_OPT_LIST_BUILD
-  int grid_oversub = 8;               // DSL_OPT_GRID_OVERSUB
-  // DSL_OPT_TILE_QUEUE: the single-domain tile kernels draw their tiles from per-XCD counters (kernels_tiled.hpp: TileFeed,
-  // dynamic mode) instead of walking a share dealt in advance.  16 launch sites x 16 ints, left at zero by every launch.
-  int tile_queue = 1;  // 0 never, 1 from 8M particles on, 2 always (tests)
-  int* walk_ctr = nullptr;
-  int walk_parity[16] = {};
-  // triangle-mesh collider (kernels_collide.hpp; dsl_collider_set_mesh): col_tri = 0: none, nothing is launched
-  int col_tri = 0, col_alloc = 0;
-  float col_radius = 0.0f, col_rest = 0.0f, col_s_thr = -1.0f;
-  bool col_cull = true;
-  TriRec* col_rec = nullptr;
-  TriBox *col_box = nullptr, *col_chunk = nullptr;
-  int* col_hits = nullptr;    // particles the last collide pass moved
-  float* col_query = nullptr; // dsl_collider_query's staging: tri, normal, coord, point in host order (10 words per particle)
-  // the cell index over the triangles (kernels_collide_index.hpp; DSL_OPT_COLLIDE_INDEX): col_ix_cells = 0: none
-  bool col_ix_on = false;
-  float col_ix_edge_req = 0.0f;  // DSL_OPT_COLLIDE_INDEX_EDGE; 0: the library's choice
-  ColIndex col_ix{};
-  int col_ix_cells = 0;
-  long long col_ix_entries = 0;
-  size_t col_ix_bytes = 0;         // its share of dev_bytes
-  bool col_last_indexed = false;   // the last collide pass or query ran the indexed kernel
-  // a mesh on a slab handle (DSL_OPT_COLLIDE_SLAB; csrc/collide_slab.hip).  col_stage: what the last integrate wrote and
-  // nobody has collided, packed or re-sorted since -- 0 nothing (dsl_collide_pass is refused), 1 everything (dsl_force_pass,
-  // Update), 2 the band layers into the output half (DSL_SPLIT_BAND), 3 the other layers (DSL_SPLIT_INNER).
-  // col_step_zeroed: the hit and visit counters were zeroed since the last neighbour build (they sum over a step's launches)
-  bool col_slab = false;
-  int col_stage = 0;
-  bool col_step_zeroed = false;
-  std::string err;
-  SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hpp)
-  // timing
-  int timing = 0;  // 0 off, 1 every kernel, 2 the step's dominant kernels only
-  std::vector<hipEvent_t> pool;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[DSL_K_COUNT];
-  double total_ms[DSL_K_COUNT] = {};
-  int64_t launches[DSL_K_COUNT] = {};
-};
-
-namespace {
-
+namespace dsl {
 int fail(dsl_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;
   else g_create_error = msg;
   return code;
 }
+}  // namespace dsl
 
-#define HIP_TRY(h, expr)                                                                             \
-  do {                                                                                               \
-    hipError_t e__ = (expr);                                                                         \
-    if (e__ != hipSuccess)                                                                           \
-      return fail((h), DSL_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));          \
-  } while (0)
+// DSL_OPT_SKIN of a DSL_MATH_FAST handle ...  (0.08: measured best of 0.06 .. 0.10 on the 16M lattice -- 9234 / 9387 /
+// 9288 M particle-steps/s, profiles/r04 -- and a tile of 4 x 4 x 3 such cells stays a fifth below the LDS image's kTCap
+// records where 0.10 sits at its edge: at 0.11 the lattice's fullest tiles no longer fit and the step takes 3.4 ms)
+constexpr float kSkinDefault = 0.07f;  // (0.08 before the lists were built at predicted positions: profiles/r04_skin_sweep_predict.jsonl)
+constexpr int kSkinDefaultParticles = 200000;  // ... of at least this many particles (measured: +24 % at 262k, +21 % at 1M, +15 % at 2M, +19 % at 16M)
 
-#define CHECK_HANDLE_ONLY(h)                              \
-  do {                                                    \
-    if (!(h)) return fail(nullptr, DSL_ERR_INVALID, "null handle"); \
-    hipError_t e__ = hipSetDevice((h)->device);           \
-    if (e__ != hipSuccess) return fail((h), DSL_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e__)); \
-  } while (0)
-int skin_settle(dsl_handle* h);
-// every entry point but the step driver itself first brings a handle that is in the middle of skin steps back to the
-// plain state (one small device read: kernels_skin.hpp)
-#define CHECK_HANDLE(h)                                   \
-  do {                                                    \
-    CHECK_HANDLE_ONLY(h);                                 \
-    if ((h)->skin_live)                                   \
-      if (int rc__ = skin_settle(h)) return rc__;         \
-  } while (0)
+// Functions that collider_host.hip or slab_link.hip call as well are defined in `namespace dsl` (declared in engine.hpp); the
+// rest of this unit's helpers are in the unnamed namespace.
+namespace {
 
 inline int grid_for(int n) { return (n + kBlock - 1) / kBlock; }
-void update_split(dsl_handle* h);
-// number of slots a per-particle launch has to cover: exact without slabs; in slab mode the
-// live count lives on the device, so cover the whole capacity (idle blocks exit at once)
-inline int launch_n(const dsl_handle* h);
 
 // Fills the device constants from the parameter block; host arithmetic mirrors
 // kernel.Build_Kernel (kernel/std_kernel.go:20-31) in float32.
@@ -325,8 +143,6 @@ int make_consts(dsl_handle* h, const dsl_params& p, DevConsts& c) {
   return DSL_OK;
 }
 
-inline int launch_n(const dsl_handle* h) { return h->c.n_ptr ? h->cap : h->n; }
-
 // the tile grid over the current cell grid (kernels_tiled.hpp: TileGrid)
 int set_tile_grid(dsl_handle* h) {
   TileGrid& tg = h->tg;
@@ -371,21 +187,6 @@ int set_cell_edge(dsl_handle* h, float edge, int tbz = kTB) {
   return set_tile_grid(h);
 }
 
-template <class T>
-int dev_alloc(dsl_handle* h, T** p, size_t count) {
-  // (64 bytes of padding: the staging quads of the tiled kernels read up to three elements past a row, the ordered
-  // scatter up to seven keys past a cell)
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T) + 64);
-  if (e != hipSuccess) return fail(h, DSL_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  // Every array starts from zeros (NewParticleArray zero-fills its slices too, particle_array.go:18-33): hipMalloc hands
-  // out whatever the previous owner left, and nothing a run computes may depend on that -- neither the padding the
-  // unaligned staging quads read past a row nor a plane that is only written for some particles.  Once per handle.
-  e = hipMemsetAsync(*p, 0, count * sizeof(T) + 64, h->stream);
-  if (e != hipSuccess) return fail(h, DSL_ERR_DEVICE, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-  h->dev_bytes += count * sizeof(T) + 64;
-  return DSL_OK;
-}
-
 // Two side arrays cost memory per GRID CELL, not per particle: the cells' key rows of the one-pass in-cell ordering (128 B
 // per cell) and the PCISPH query rows (512 B per cell).  In the dam-break box (8 x the fluid's volume) that is 128 / 512 B
 // per particle; a tall or sparse domain multiplies it.  Each is therefore only allocated within a budget -- the larger of
@@ -397,6 +198,8 @@ bool side_array_fits(const dsl_handle* h, size_t bytes) {
   return bytes <= budget;
 }
 
+}  // namespace
+namespace dsl {
 hipEvent_t get_event(dsl_handle* h) {
   if (!h->pool.empty()) {
     hipEvent_t e = h->pool.back();
@@ -407,22 +210,8 @@ hipEvent_t get_event(dsl_handle* h) {
   (void)hipEventCreate(&e);
   return e;
 }
-
-template <class F>
-int timed(dsl_handle* h, int kid, F&& launch) {
-  if (h->timing == 1 || (h->timing == 2 && (kid == DSL_K_DENSITY || kid == DSL_K_FORCE_INTEGRATE || kid == DSL_K_PCI_DENSITY))) {
-    hipEvent_t a = get_event(h), b = get_event(h);
-    (void)hipEventRecord(a, h->stream);
-    launch();
-    (void)hipEventRecord(b, h->stream);
-    h->pending[kid].emplace_back(a, b);
-  } else {
-    launch();
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, DSL_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-  return DSL_OK;
-}
+}  // namespace dsl
+namespace {
 
 int drain_timing(dsl_handle* h) {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -440,25 +229,6 @@ int drain_timing(dsl_handle* h) {
   }
   return DSL_OK;
 }
-
-CSoa3 cpos(dsl_handle* h) { return {h->pv[h->cur_pv][0], h->pv[h->cur_pv][1], h->pv[h->cur_pv][2]}; }
-CSoa3 cvel(dsl_handle* h) { return {h->pv[h->cur_pv][3], h->pv[h->cur_pv][4], h->pv[h->cur_pv][5]}; }
-Soa3 mpos(dsl_handle* h, int w) { return {h->pv[w][0], h->pv[w][1], h->pv[w][2]}; }
-Soa3 mvel(dsl_handle* h, int w) { return {h->pv[w][3], h->pv[w][4], h->pv[w][5]}; }
-Soa3 mfrc(dsl_handle* h) { return {h->frc[h->cur_f][0], h->frc[h->cur_f][1], h->frc[h->cur_f][2]}; }
-CSoa3 cfrc(dsl_handle* h) { return {h->frc[h->cur_f][0], h->frc[h->cur_f][1], h->frc[h->cur_f][2]}; }
-Soa3 mpcip(dsl_handle* h) { return {h->pci[h->cur_pci][0], h->pci[h->cur_pci][1], h->pci[h->cur_pci][2]}; }
-Soa3 mpciv(dsl_handle* h) { return {h->pci[h->cur_pci][3], h->pci[h->cur_pci][4], h->pci[h->cur_pci][5]}; }
-Soa3 mxsph(dsl_handle* h) { return {h->xsph[0], h->xsph[1], h->xsph[2]}; }
-Soa3 mgterm(dsl_handle* h) { return {h->gterm[0], h->gterm[1], h->gterm[2]}; }
-constexpr Soa3 kNoSoa3{nullptr, nullptr, nullptr};
-CSoa3 as_const(Soa3 a) { return {a.x, a.y, a.z}; }
-// the PCISPH predictor state, or three nulls while PCISPH is not running
-Soa3 mpcip_if_active(dsl_handle* h) { return h->pci_active ? mpcip(h) : kNoSoa3; }
-Soa3 mpciv_if_active(dsl_handle* h) { return h->pci_active ? mpciv(h) : kNoSoa3; }
-
-inline int n_fluid_of(const dsl_handle* h) { return h->n - h->nb; }
-Bnd bnd_of(const dsl_handle* h) { return Bnd{h->nb > 0 ? h->ids[h->cur_ids] : nullptr, n_fluid_of(h)}; }
 
 Neigh neigh(const dsl_handle* h) {
   if (h->lsh) return Neigh{h->cell_start, h->lsh_samples, h->hashv, h->lsh_bits, h->prm.lsh_buckets};
@@ -545,6 +315,8 @@ void launch_query_tile_tables(dsl_handle* h, bool rows, bool keep_counts) {
                      SkinGate{nullptr}, keep_counts);
 }
 
+}  // namespace
+namespace dsl {
 int build_grid(dsl_handle* h, bool carry_derived) {
   if (h->split_pending) return fail(h, DSL_ERR_INVALID, "a split force pass is in flight: finish it with DSL_SPLIT_INNER");
   if (h->lsh) return build_lsh(h);
@@ -643,6 +415,8 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   }
   return DSL_OK;
 }
+}  // namespace dsl
+namespace {
 
 int ensure_grid(dsl_handle* h) { return h->grid_valid ? DSL_OK : build_grid(h, true); }
 
@@ -666,11 +440,15 @@ void by_math(dsl_handle* h, F&& f) {
 bool exact_tiled(const dsl_handle* h) {
   return h->prm.math_mode == DSL_MATH_EXACT && !h->lsh && h->c.slab_axis < 0 && h->nmask != nullptr;
 }
+}  // namespace
+namespace dsl {
 bool use_tiled(const dsl_handle* h) {
   if (h->prm.math_mode != DSL_MATH_FAST || h->lsh) return false;
   if (h->c.wcsph_viscosity && h->c.visc_running_mass && h->c.mass != 1.0f) return false;
   return true;
 }
+}  // namespace dsl
+namespace {
 // `lists`: the skin step's list kernels -- their tiles cost the same and their workgroups stay persistent
 int persistent_grid(const dsl_handle* h, int blocks_per_cu, bool lists = false) {
   // DSL_OPT_GRID_OVERSUB (default 8): eight times the workgroups the chip holds, each with an eighth of the share -- the
@@ -717,6 +495,8 @@ int* walk_ctr_of(dsl_handle* h, int site) {
   return h->walk_ctr + 16 * site + 8 * h->walk_parity[site];
 }
 
+}  // namespace
+namespace dsl {
 int density_pass(dsl_handle* h) {
   const DevConsts& c = h->c;
   CSoa3 p = cpos(h);
@@ -762,7 +542,7 @@ int density_pass(dsl_handle* h) {
 // part 0: every tile, then the state flips to the integrated arrays.  Split slab step:
 // part 1 = band tiles only (state unchanged, dsl_slab_pack_band reads the output arrays next),
 // part 2 = the remaining tiles, then the flip.
-int force_integrate(dsl_handle* h, int part = 0) {
+int force_integrate(dsl_handle* h, int part) {
   DevConsts c = h->c;
   c.split_part = part;
   if (part == 2) {  // an interior particle that reaches a packed band moved further than the margin
@@ -843,6 +623,8 @@ int force_integrate(dsl_handle* h, int part = 0) {
   h->grid_valid = false;     // positions moved
   return DSL_OK;
 }
+}  // namespace dsl
+namespace {
 
 int gradient_pass(dsl_handle* h, int honour_done) {
   const DevConsts& c = h->c;
@@ -887,265 +669,6 @@ int update_pass(dsl_handle* h, bool use_xs = false) {
   h->forces_uniform = true;
   h->press_zero = true;
   h->grid_valid = false;
-  h->masks_valid = false;
-  return DSL_OK;
-}
-
-// ---- the cell index over the collider's triangles (kernels_collide_index.hpp; DSL_OPT_COLLIDE_INDEX) ----
-void col_index_free(dsl_handle* h) {
-  (void)hipFree(const_cast<int*>(h->col_ix.start));
-  (void)hipFree(const_cast<int*>(h->col_ix.list));
-  (void)hipFree(const_cast<int*>(h->col_ix.always));
-  (void)hipFree(h->col_ix.counters);
-  h->dev_bytes -= h->col_ix_bytes;
-  h->col_ix = ColIndex{};
-  h->col_ix_bytes = 0;
-  h->col_ix_cells = 0;
-  h->col_ix_entries = 0;
-}
-
-// What an index over the mesh that is set would be: the grid (origin, top, edge, dims of `ix`), its cells and entries.
-struct ColIndexPlan {
-  ColIndex ix{};
-  long long cells = 0, entries = 0;
-  int n_reg = 0;
-};
-
-// The grid for cell edge `edge`: false if it has more than kColIndexMaxCells cells.  dims[k] = the cell of top[k] + 1, by
-// col_cell's expression (the kernels clamp to dims, so the host's rounding of it decides nothing but the grid's size).
-bool col_index_grid(ColIndexPlan* pl, float edge) {
-  double cells = 1.0;
-  for (int k = 0; k < 3; ++k) {
-    const double d = std::floor((double)((pl->ix.top[k] - pl->ix.origin[k]) / edge)) + 1.0;
-    if (!(d >= 1.0 && d <= (double)kColIndexMaxCells)) return false;
-    pl->ix.dims[k] = (int)d;
-    cells *= d;
-  }
-  if (cells > (double)kColIndexMaxCells) return false;
-  pl->ix.edge = edge;
-  pl->cells = (long long)cells;
-  return true;
-}
-
-// Plans the index for cell edge `edge_req` (0: the library's choice) without touching the handle's state.  Blocking.
-// The library's choice: the mean over the regular triangles of their padded box's mean extent, doubled until the grid
-// has at most 2^22 cells and the lists at most max(2^20, 64 T) entries.  An edge the host sets is taken or refused.
-int col_index_plan(dsl_handle* h, float edge_req, ColIndexPlan* pl) {
-  const int T = h->col_tri;
-  ColBounds* dpart = nullptr;
-  unsigned long long* dtotal = nullptr;
-  std::vector<ColBounds> part(kColBoundsWaves);
-  hipError_t e = hipMalloc((void**)&dpart, kColBoundsWaves * sizeof(ColBounds));
-  if (e == hipSuccess) e = hipMalloc((void**)&dtotal, sizeof(unsigned long long));
-  auto done = [&](int rc) {
-    (void)hipFree(dpart);
-    (void)hipFree(dtotal);
-    return rc;
-  };
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return done(fail(h, DSL_ERR_NOMEM, "collider index: hipMalloc failed"));
-  }
-  launch_index_bounds(h->stream, T, h->col_box, dpart);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), dpart, kColBoundsWaves * sizeof(ColBounds), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
-  double ext = 0.0;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (const ColBounds& b : part) {  // (in order: the same sum every time)
-    pl->n_reg += b.n_reg;
-    ext += b.ext;
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = std::fmin(lo[k], b.lo[k]);
-      hi[k] = std::fmax(hi[k], b.hi[k]);
-    }
-  }
-  const long long budget = col_index_max_entries(T);
-  const std::string budget_text = "the index's budget is 2^22 cells and max(2^20, 64 T) = " + std::to_string(budget) + " list entries";
-  if (pl->n_reg == 0) {  // every triangle is on the always-list: one empty cell
-    for (int k = 0; k < 3; ++k) pl->ix.origin[k] = pl->ix.top[k] = 0.0f, pl->ix.dims[k] = 1;
-    pl->ix.edge = edge_req > 0.0f ? edge_req : 1.0f;
-    pl->cells = 1;
-    pl->entries = T;
-    return done(DSL_OK);
-  }
-  for (int k = 0; k < 3; ++k) pl->ix.origin[k] = lo[k], pl->ix.top[k] = hi[k];
-  auto entries_of = [&](unsigned long long* out) {  // the regular triangles' entries in pl's grid
-    hipError_t e2 = hipMemsetAsync(dtotal, 0, sizeof(unsigned long long), h->stream);
-    if (e2 == hipSuccess) {
-      launch_index_total(h->stream, T, h->col_box, pl->ix, dtotal);
-      e2 = hipGetLastError();
-    }
-    if (e2 == hipSuccess) e2 = hipMemcpyAsync(out, dtotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(h->stream);
-    return e2;
-  };
-  unsigned long long reg_entries = 0;
-  if (edge_req > 0.0f) {
-    if (!col_index_grid(pl, edge_req))
-      return done(fail(h, DSL_ERR_INVALID, "DSL_OPT_COLLIDE_INDEX_EDGE: too many cells over this mesh; " + budget_text));
-    if ((e = entries_of(&reg_entries)) != hipSuccess)
-      return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
-    if ((long long)reg_entries + (T - pl->n_reg) > budget)
-      return done(fail(h, DSL_ERR_INVALID, "DSL_OPT_COLLIDE_INDEX_EDGE: too many list entries over this mesh; " + budget_text));
-  } else {
-    float edge = (float)(ext / pl->n_reg);
-    if (!(edge > 0.0f)) edge = 1.0f;
-    for (;; edge *= 2.0f) {
-      if (!std::isfinite(edge)) return done(fail(h, DSL_ERR_INVALID, "collider index: no cell edge fits this mesh; " + budget_text));
-      if (!col_index_grid(pl, edge)) continue;
-      if ((e = entries_of(&reg_entries)) != hipSuccess)
-        return done(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e)));
-      if ((long long)reg_entries + (T - pl->n_reg) <= budget) break;
-    }
-  }
-  pl->entries = (long long)reg_entries + (T - pl->n_reg);
-  return done(DSL_OK);
-}
-
-// Builds the planned index on the device (any earlier one is freed first).  Blocking.  On failure the handle has no
-// index and the list walk runs.
-int col_index_build(dsl_handle* h, const ColIndexPlan& pl) {
-  col_index_free(h);
-  const int T = h->col_tri, cells = (int)pl.cells, n_always = T - pl.n_reg, n_pad = col_index_pad(cells);
-  ColIndex ix = pl.ix;
-  ix.n_always = n_always;
-  int *start = nullptr, *list = nullptr, *always = nullptr, *cnt = nullptr, *tmp = nullptr;
-  unsigned long long *counters = nullptr, *dtotal = nullptr;
-  size_t bytes = 0;
-  auto fin = [&](int rc) {  // scratch goes either way; the index's own arrays only on failure
-    (void)hipFree(cnt);
-    (void)hipFree(tmp);
-    (void)hipFree(dtotal);
-    if (rc) {
-      (void)hipFree(start);
-      (void)hipFree(list);
-      (void)hipFree(always);
-      (void)hipFree(counters);
-    }
-    return rc;
-  };
-  auto nomem = [&] {
-    (void)hipGetLastError();
-    return fin(fail(h, DSL_ERR_NOMEM, "collider index: hipMalloc failed; the list walk runs"));
-  };
-  auto dev = [&](hipError_t e) { return fin(fail(h, DSL_ERR_DEVICE, std::string("collider index: ") + hipGetErrorString(e))); };
-  if (hipMalloc((void**)&start, (size_t)n_pad * sizeof(int)) != hipSuccess) return nomem();
-  if (hipMalloc((void**)&cnt, (size_t)n_pad * sizeof(int)) != hipSuccess) return nomem();
-  if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) return nomem();
-  if (hipMalloc((void**)&dtotal, sizeof(unsigned long long)) != hipSuccess) return nomem();
-  if (n_always > 0 && hipMalloc((void**)&always, (size_t)n_always * sizeof(int)) != hipSuccess) return nomem();
-  bytes += (size_t)n_pad * sizeof(int) + 2 * sizeof(unsigned long long) + (size_t)n_always * sizeof(int);
-  ix.start = start;
-  ix.always = always;
-  ix.counters = counters;
-  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n_pad * sizeof(int), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), h->stream);
-  unsigned long long padded = 0;
-  if (e == hipSuccess) {
-    launch_index_count(h->stream, T, h->col_box, ix, n_pad, cnt, start, dtotal);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&padded, dtotal, sizeof(padded), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return dev(e);
-  if (padded > 0x7fffffffull) return fin(fail(h, DSL_ERR_NOMEM, "collider index: the cell lists pass 2^31 entries; the list walk runs"));
-  const size_t n_list = (size_t)std::max<unsigned long long>(padded, 4);
-  if (hipMalloc((void**)&list, n_list * sizeof(int)) != hipSuccess) return nomem();
-  if (hipMalloc((void**)&tmp, n_list * sizeof(int)) != hipSuccess) return nomem();
-  bytes += n_list * sizeof(int);
-  ix.list = list;
-  e = hipMemsetAsync(list, kColNone & 0xff, n_list * sizeof(int), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)n_pad * sizeof(int), h->stream);
-  if (e == hipSuccess) {
-    launch_index_fill(h->stream, T, h->col_box, ix, cells, cnt, list, tmp, always);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return dev(e);
-  h->col_ix = ix;
-  h->col_ix_cells = cells;
-  h->col_ix_entries = pl.entries;
-  h->col_ix_bytes = bytes;
-  h->dev_bytes += bytes;
-  return fin(DSL_OK);
-}
-
-// The index follows the mesh, the option and the edge: called when any of them has changed.  A refused edge
-// (DSL_ERR_INVALID) leaves the index that was built.
-int col_index_update(dsl_handle* h, bool on, float edge_req) {
-  if (!on || h->col_tri == 0) {
-    col_index_free(h);
-    return DSL_OK;
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the index that is replaced)
-  ColIndexPlan pl;
-  if (int rc = col_index_plan(h, edge_req, &pl)) return rc;
-  return col_index_build(h, pl);
-}
-
-// The collider pass (kernels_collide.hpp): Mesh.Collision for every fluid particle, then the build-defined response, in
-// place on the current state.  Without a mesh nothing is launched.  dsl_stats.max_vel / max_f stay what Update saw.
-ColMesh col_mesh(const dsl_handle* h) {
-  return ColMesh{h->col_rec, h->col_box, h->col_chunk, h->col_tri, h->col_s_thr, h->col_rest, h->col_cull ? 1 : 0};
-}
-// The launch of either collide kernel: the walk over the cell index if one is built and the broad phase is on (cull 0
-// keeps meaning "every pair is tested"), the list walk otherwise.
-int collide_launch(dsl_handle* h, bool respond, ColQuery q, int* hits) {
-  h->col_last_indexed = h->col_ix_cells > 0 && h->col_cull;
-  if (h->col_last_indexed) {
-    HIP_TRY(h, hipMemsetAsync(h->col_ix.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-    launch_collide_indexed(h->stream, respond, h->n, h->c.dt, bnd_of(h), col_mesh(h), h->col_ix, mpos(h, h->cur_pv),
-                           mvel(h, h->cur_pv), q, hits);
-  } else {
-    launch_collide(h->stream, respond, h->n, h->c.dt, bnd_of(h), col_mesh(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), q, hits);
-  }
-  return DSL_OK;
-}
-// The pass on a slab rank (csrc/collide_slab.hip; the rules are at dsl_collide_pass in include/dslsph.h): exactly the
-// slots the last integrate wrote.  After the band launch of the split step these lie in the OUTPUT half of the state
-// and the state has not flipped; the pre-step coordinates that select band or inner slots are in the other half.
-int collide_pass_slab(dsl_handle* h) {
-  const int stage = h->col_stage;
-  if (stage == 0)
-    return fail(h, DSL_ERR_INVALID,
-                "dsl_collide_pass: on a slab handle the order is integrate -> collide -> pack / append / neighbour build, one "
-                "collide per integrate: nothing has been integrated since the last collide, dsl_slab_pack, dsl_slab_pack_band, "
-                "dsl_slab_append, dsl_slab_exchange or dsl_build_neighbours");
-  const int out = stage == 2 ? h->cur_pv ^ 1 : h->cur_pv;
-  const int sel = stage - 1;
-  const float* old_axis = sel != 0 ? h->pv[out ^ 1][h->c.slab_axis] : nullptr;
-  const bool indexed = h->col_ix_cells > 0 && h->col_cull;
-  if (!h->col_step_zeroed) {  // the counters sum over the launches of one step: band + inner
-    HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
-    if (indexed) HIP_TRY(h, hipMemsetAsync(h->col_ix.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-    h->col_step_zeroed = true;
-  }
-  h->col_last_indexed = indexed;
-  const int rc = timed(h, DSL_K_COLLIDE, [&] {
-    launch_collide_slab(h->stream, h->cap, h->c, sel, old_axis, col_mesh(h), indexed ? &h->col_ix : nullptr, mpos(h, out),
-                        mvel(h, out), h->col_hits);
-  });
-  if (rc) return rc;
-  // (a host that packs the band on a stream of its own waits for this event: it has to cover the band's collide too)
-  if (stage == 2 && h->ev_band) HIP_TRY(h, hipEventRecord(h->ev_band, h->stream));
-  h->col_stage = 0;
-  if (stage != 2) {  // (the band launch's state is still the pre-step one: its grid and masks serve the inner launch)
-    h->grid_valid = false;
-    h->masks_valid = false;
-  }
-  return DSL_OK;
-}
-int collide_pass(dsl_handle* h) {
-  if (h->col_tri == 0) return DSL_OK;
-  if (h->c.n_ptr) return collide_pass_slab(h);
-  HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
-  int lrc = DSL_OK;
-  int rc = timed(h, DSL_K_COLLIDE, [&] { lrc = collide_launch(h, true, ColQuery{}, h->col_hits); });
-  if (lrc) return lrc;
-  if (rc) return rc;
-  h->grid_valid = false;  // positions moved
   h->masks_valid = false;
   return DSL_OK;
 }
@@ -1307,10 +830,6 @@ int alloc_query_bins(dsl_handle* h) {
 }
 
 }  // namespace
-
-#include "slab_link.hpp"
-
-extern "C" {
 
 const char* dsl_version(void) { return "dslsph 0.1 (gfx950)"; }
 
@@ -2072,6 +1591,9 @@ int skin_step(dsl_handle* h) {
   return DSL_OK;
 }
 
+}  // namespace
+
+namespace dsl {
 // back to the plain state: which slot -> particle map is current is the device's knowledge (one small read)
 int skin_settle(dsl_handle* h) {
   SkinState s{};
@@ -2086,8 +1608,7 @@ int skin_settle(dsl_handle* h) {
   h->dens_fresh = false;
   return set_cell_edge(h, h->c.h);
 }
-
-}  // namespace
+}  // namespace dsl
 
 int dsl_wcsph_step(dsl_handle* h, int nsteps) {
   CHECK_HANDLE_ONLY(h);
@@ -2256,106 +1777,6 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// triangle-mesh collider (kernels_collide.hpp)
-// ---------------------------------------------------------------------------------------
-int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* normals, size_t n_triangles, float radius,
-                          float restitution) {
-  CHECK_HANDLE(h);
-  if ((h->c.slab_axis >= 0 || h->c.n_ptr) && !h->col_slab)  // (DSL_OPT_COLLIDE_SLAB: every rank sets the same mesh)
-    return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_set_mesh: a collider mesh is not supported in slab mode");
-  if (n_triangles == 0) {  // removes the mesh (the arrays stay for the next one; the cell index goes)
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->col_tri = 0;
-    h->col_last_indexed = false;
-    col_index_free(h);
-    return DSL_OK;
-  }
-  if (!vertices || !normals) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: null vertex or normal pointer");
-  if (n_triangles > ((size_t)1 << 24)) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: more than 2^24 triangles");
-  const int T = (int)n_triangles, nchunk = (T + kColChunk - 1) / kColChunk;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the mesh that is replaced)
-  h->col_tri = 0;  // no mesh until the new one is whole: a failure below leaves the handle without a collider
-  h->col_last_indexed = false;
-  col_index_free(h);
-  if (T > h->col_alloc) {
-    (void)hipFree(h->col_rec);
-    (void)hipFree(h->col_box);
-    (void)hipFree(h->col_chunk);
-    h->col_rec = nullptr;
-    h->col_box = h->col_chunk = nullptr;
-    h->col_alloc = 0;
-    int rc = DSL_OK;
-    if ((rc = dev_alloc(h, &h->col_rec, (size_t)T))) return rc;
-    if ((rc = dev_alloc(h, &h->col_box, (size_t)T))) return rc;
-    if ((rc = dev_alloc(h, &h->col_chunk, (size_t)nchunk))) return rc;
-    h->col_alloc = T;
-  }
-  if (!h->col_hits)
-    if (int rc = dev_alloc(h, &h->col_hits, 1)) return rc;
-  float* in = nullptr;  // the caller's arrays: 9 T vertices, then 3 T normals
-  if (hipMalloc((void**)&in, (size_t)12 * T * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, DSL_ERR_NOMEM, "dsl_collider_set_mesh: hipMalloc failed");
-  }
-  hipError_t e = hipMemcpyAsync(in, vertices, (size_t)9 * T * sizeof(float), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(in + (size_t)9 * T, normals, (size_t)3 * T * sizeof(float), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    launch_collide_prep(h->stream, T, in, in + (size_t)9 * T, radius, h->col_rec, h->col_box, h->col_chunk);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (host pointers are never retained after a call returns)
-  (void)hipFree(in);
-  if (e != hipSuccess) return fail(h, DSL_ERR_DEVICE, std::string("dsl_collider_set_mesh: ") + hipGetErrorString(e));
-  // `Mag(q) <= r` on the float32 sum of squares: Mag is float32(sqrt(float64(s))) (vector.go:301-308), monotone in s, so
-  // the test is s <= the largest float whose Mag is <= r.  None for a negative or NaN radius (s >= 0 or NaN: -1 fails all).
-  float thr = -1.0f;
-  if (radius >= 0.0f) {
-    auto mag = [](float s) { return (float)std::sqrt((double)s); };
-    thr = radius * radius;
-    if (!(thr <= 3.4028235e38f)) thr = 3.4028235e38f;
-    while (thr > 0.0f && mag(thr) > radius) thr = std::nextafter(thr, 0.0f);
-    while (thr < INFINITY && mag(std::nextafter(thr, INFINITY)) <= radius) thr = std::nextafter(thr, INFINITY);
-  }
-  h->col_s_thr = thr;
-  h->col_radius = radius;
-  h->col_rest = restitution;
-  h->col_tri = T;
-  // the cell index, if it is switched on: a failure here leaves the mesh set, without an index (the list walk runs)
-  return col_index_update(h, h->col_ix_on, h->col_ix_edge_req);
-}
-
-int dsl_collide_pass(dsl_handle* h) {
-  CHECK_HANDLE(h);
-  return collide_pass(h);
-}
-
-int dsl_collider_query(dsl_handle* h, int32_t* tri, float* normal, float* coord, float* point) {
-  CHECK_HANDLE(h);
-  if (h->c.n_ptr) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_collider_query: not available in slab mode");
-  if (h->ids_global) return fail(h, DSL_ERR_INVALID, "dsl_collider_query: host order is gone after dsl_set_ids");
-  const size_t nf = (size_t)n_fluid_of(h);
-  if (h->col_tri == 0) {  // Mesh.Collision of an empty mesh: no collision, empty vectors (mesh.go:56)
-    if (tri) std::fill(tri, tri + nf, -1);
-    for (float* a : {normal, coord, point})
-      if (a) std::fill(a, a + 3 * nf, 0.0f);
-    return DSL_OK;
-  }
-  if (!h->col_query)
-    if (int rc = dev_alloc(h, &h->col_query, (size_t)10 * h->cap)) return rc;
-  float* qb = h->col_query;
-  const ColQuery q{tri ? reinterpret_cast<int*>(qb) : nullptr, normal ? qb + nf : nullptr, coord ? qb + 4 * nf : nullptr,
-                   point ? qb + 7 * nf : nullptr, h->ids[h->cur_ids]};
-  if (int rc = collide_launch(h, false, q, nullptr)) return rc;
-  HIP_TRY(h, hipGetLastError());
-  if (tri) HIP_TRY(h, hipMemcpyAsync(tri, q.tri, nf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (normal) HIP_TRY(h, hipMemcpyAsync(normal, q.normal, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (coord) HIP_TRY(h, hipMemcpyAsync(coord, q.coord, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (point) HIP_TRY(h, hipMemcpyAsync(point, q.point, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DSL_OK;
-}
-
 int dsl_pcisph_begin(dsl_handle* h) {
   CHECK_HANDLE(h);
   if (int rc = alloc_pci(h)) return rc;
@@ -2420,7 +1841,9 @@ bool pci_tiled(const dsl_handle* h) {
   return h->prm.math_mode == DSL_MATH_FAST && !(h->c.visc_running_mass && h->c.mass != 1.0f);
 }
 bool pci_extra_terms(const dsl_handle* h) { return h->c.xsph_eps != 0.0f || h->c.st_kappa != 0.0f; }
+}  // namespace
 
+namespace dsl {
 // NN, DensityAll, ViscousAll (pcisph_darwin.go:43-45) and the loop set-up
 int pci_begin_step(dsl_handle* h) {
   const DevConsts& c = h->c;
@@ -2585,7 +2008,7 @@ int pci_end_step(dsl_handle* h) {                // Update :101 (positions advec
   h->pci_steps++;
   return DSL_OK;
 }
-}  // namespace
+}  // namespace dsl
 
 int dsl_pcisph_step(dsl_handle* h, int nsteps) {
   CHECK_HANDLE(h);
@@ -2685,7 +2108,7 @@ size_t dsl_slab_message_floats_for(dsl_handle* h, int cap_full, int cap_xonly) {
   return (size_t)(cap_full + 1) * dsl_slab_record_floats(h) + (size_t)cap_xonly * kRecordX;
 }
 
-namespace {
+namespace dsl {
 // band cell layers: every cell that reaches within width + margin of a slab plane
 void update_split(dsl_handle* h) {
   DevConsts& c = h->c;
@@ -2721,7 +2144,7 @@ void update_split(dsl_handle* h) {
   }
   if (c.split_ch < c.split_cl) c.split_ch = c.split_cl;  // thin slab: every layer is a band layer
 }
-}  // namespace
+}  // namespace dsl
 
 int dsl_slab_split(dsl_handle* h, float width, float margin) {
   CHECK_HANDLE(h);
@@ -2734,7 +2157,7 @@ int dsl_slab_split(dsl_handle* h, float width, float margin) {
   return DSL_OK;
 }
 
-namespace {
+namespace dsl {
 int slab_pack_on(dsl_handle* h, hipStream_t st, float width_full, float width, bool from_output, float* dev_lo,
                  float* dev_hi, int cap_full, int cap_x) {
   SlabBands sb;
@@ -2763,6 +2186,8 @@ int slab_pack_on(dsl_handle* h, hipStream_t st, float width_full, float width, b
   h->col_stage = 0;  // (slab collider: a collide behind the pack would make the message stale)
   return DSL_OK;
 }
+}  // namespace dsl
+namespace {
 int slab_pack_check(dsl_handle* h, const char* who, float width_full, float width, float* dev_lo, float* dev_hi,
                     int cap_full, int cap_x) {
   if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, std::string(who) + ": no slab configured");
@@ -2814,8 +2239,9 @@ int dsl_force_pass_split(dsl_handle* h, int phase) {
   return fail(h, DSL_ERR_INVALID, "dsl_force_pass_split: bad phase");
 }
 
-static int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const float* dev_message_b, int cap_full,
-                               int cap_xonly, float shift_a, float shift_b) {
+namespace dsl {
+int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const float* dev_message_b, int cap_full, int cap_xonly,
+                        float shift_a, float shift_b) {
   CHECK_HANDLE(h);
   if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_append: no slab configured");
   if ((!dev_message_a && !dev_message_b) || cap_full < 0 || cap_xonly < 0)
@@ -2838,6 +2264,7 @@ static int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const 
   h->dens_held = false;  // (the appended records have no densities yet; the slab step's sort does not carry them)
   return DSL_OK;
 }
+}  // namespace dsl
 
 int dsl_slab_append2(dsl_handle* h, const float* dev_message_a, const float* dev_message_b, int cap_full,
                      int cap_xonly) {
@@ -2889,590 +2316,6 @@ int dsl_slab_overflow(dsl_handle* h, int* high_water) {
   int32_t st[4] = {0, 0, 0, 0};
   if (int rc = dsl_slab_status(h, st, 0)) return rc;
   if (high_water) *high_water = st[0];
-  return DSL_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// multi-GPU behind the C ABI: communicator, slab link, step drivers (slab_link.hpp)
-// ---------------------------------------------------------------------------------------
-const char* dsl_comm_last_error(void) { return g_comm_error.c_str(); }
-
-int dsl_comm_unique_id(uint8_t id[DSL_COMM_ID_BYTES]) {
-  if (!id) return DSL_ERR_INVALID;
-  if (!rccl_load()) {
-    g_comm_error = rccl().err;
-    return DSL_ERR_UNSUPPORTED;
-  }
-  static_assert(DSL_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
-  ncclUniqueId u;
-  const ncclResult_t r = rccl().GetUniqueId(&u);
-  if (r != ncclSuccess) {
-    g_comm_error = std::string("ncclGetUniqueId: ") + rccl().GetErrorString(r);
-    return DSL_ERR_DEVICE;
-  }
-  std::memcpy(id, u.internal, DSL_COMM_ID_BYTES);
-  return DSL_OK;
-}
-
-int dsl_comm_create(int nranks, int rank, const uint8_t id[DSL_COMM_ID_BYTES], int device, dsl_comm** out) {
-  if (!out || !id || nranks < 1 || rank < 0 || rank >= nranks) {
-    g_comm_error = "dsl_comm_create: bad argument";
-    return DSL_ERR_INVALID;
-  }
-  *out = nullptr;
-  if (!rccl_load()) {
-    g_comm_error = rccl().err;
-    return DSL_ERR_UNSUPPORTED;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_comm_error = "dsl_comm_create: hipSetDevice failed";
-    return DSL_ERR_DEVICE;
-  }
-  ncclUniqueId u;
-  std::memcpy(u.internal, id, DSL_COMM_ID_BYTES);
-  dsl_comm* c = new (std::nothrow) dsl_comm();
-  if (!c) return DSL_ERR_NOMEM;
-  const ncclResult_t r = rccl().CommInitRank(&c->comm, nranks, u, rank);
-  if (r != ncclSuccess) {
-    g_comm_error = std::string("ncclCommInitRank: ") + rccl().GetErrorString(r);
-    delete c;
-    return DSL_ERR_DEVICE;
-  }
-  c->nranks = nranks;
-  c->rank = rank;
-  c->device = device;
-  *out = c;
-  return DSL_OK;
-}
-
-int dsl_comm_create_all(int ndev, const int* devices, dsl_comm** out) {
-  if (!out || !devices || ndev < 1) {
-    g_comm_error = "dsl_comm_create_all: bad argument";
-    return DSL_ERR_INVALID;
-  }
-  if (!rccl_load()) {
-    g_comm_error = rccl().err;
-    return DSL_ERR_UNSUPPORTED;
-  }
-  std::vector<ncclComm_t> comms((size_t)ndev);
-  const ncclResult_t r = rccl().CommInitAll(comms.data(), ndev, devices);
-  if (r != ncclSuccess) {
-    g_comm_error = std::string("ncclCommInitAll: ") + rccl().GetErrorString(r);
-    return DSL_ERR_DEVICE;
-  }
-  for (int k = 0; k < ndev; ++k) {
-    dsl_comm* c = new dsl_comm();
-    c->comm = comms[(size_t)k];
-    c->nranks = ndev;
-    c->rank = k;
-    c->device = devices[k];
-    out[k] = c;
-  }
-  return DSL_OK;
-}
-
-int dsl_comm_create_custom(int nranks, int rank, int device, const dsl_transport* t, dsl_comm** out) {
-  if (!out || !t || nranks < 1 || rank < 0 || rank >= nranks || !t->group_start || !t->group_end || !t->send || !t->recv ||
-      !t->all_reduce_max_u32) {
-    g_comm_error = "dsl_comm_create_custom: bad argument (every callback of dsl_transport is required)";
-    return DSL_ERR_INVALID;
-  }
-  dsl_comm* c = new (std::nothrow) dsl_comm();
-  if (!c) return DSL_ERR_NOMEM;
-  c->custom = true;
-  c->tr = *t;
-  c->nranks = nranks;
-  c->rank = rank;
-  c->device = device;
-  *out = c;
-  return DSL_OK;
-}
-
-int dsl_comm_destroy(dsl_comm* c) {
-  if (!c) return DSL_OK;
-  if (c->comm && !c->custom && rccl().lib) (void)rccl().CommDestroy(c->comm);
-  delete c;
-  return DSL_OK;
-}
-
-int dsl_comm_count(dsl_comm* c, int* nranks) {
-  if (!c || !nranks) {
-    g_comm_error = "dsl_comm_count: bad argument";
-    return DSL_ERR_INVALID;
-  }
-  *nranks = c->nranks;
-  if (!c->custom && c->comm) {
-    int n = 0;
-    const ncclResult_t r = rccl().CommCount(c->comm, &n);
-    if (r != ncclSuccess) {
-      g_comm_error = std::string("ncclCommCount: ") + rccl().GetErrorString(r);
-      return DSL_ERR_DEVICE;
-    }
-    *nranks = n;
-  }
-  return DSL_OK;
-}
-
-int dsl_create_multi(const dsl_params* params, int ndev, const int* devices, dsl_handle** handles, dsl_comm** comms) {
-  if (!params || !devices || !handles || !comms || ndev < 1) return fail(nullptr, DSL_ERR_INVALID, "dsl_create_multi: bad argument");
-  for (int k = 0; k < ndev; ++k) handles[k] = nullptr, comms[k] = nullptr;
-  for (int k = 0; k < ndev; ++k) {
-    if (int rc = dsl_create(&params[k], devices[k], &handles[k])) {
-      for (int j = 0; j < k; ++j) (void)dsl_destroy(handles[j]), handles[j] = nullptr;
-      return rc;
-    }
-  }
-  if (int rc = dsl_comm_create_all(ndev, devices, comms)) {
-    for (int j = 0; j < ndev; ++j) (void)dsl_destroy(handles[j]), handles[j] = nullptr;
-    return fail(nullptr, rc, g_comm_error);
-  }
-  return DSL_OK;
-}
-
-int dsl_slab_detach(dsl_handle* h) {
-  if (!h || !h->link) return DSL_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  SlabLink* L = h->link;
-  if (L->comm_stream) (void)hipStreamSynchronize(L->comm_stream);
-  for (int k = 0; k < 2; ++k) {
-    (void)hipFree(L->send[k]);
-    (void)hipFree(L->recv[k]);
-  }
-  (void)hipFree(L->dev_words);
-  (void)hipFree(L->bal.dev_counts);
-  if (L->ev_pack) (void)hipEventDestroy(L->ev_pack);
-  if (L->ev_xfer) (void)hipEventDestroy(L->ev_xfer);
-  if (L->comm_stream) (void)hipStreamDestroy(L->comm_stream);
-  delete L;
-  h->link = nullptr;
-  return DSL_OK;
-}
-
-int dsl_slab_attach(dsl_handle* h, dsl_comm* comm, int lo_rank, int hi_rank, float width_full, float width, int cap_full,
-                    int cap_xonly, int overlap) {
-  CHECK_HANDLE(h);
-  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_attach: call dsl_slab_config first");
-  if ((lo_rank >= 0 || hi_rank >= 0) && !comm) return fail(h, DSL_ERR_INVALID, "dsl_slab_attach: neighbours need a communicator");
-  if (comm && (lo_rank >= comm->nranks || hi_rank >= comm->nranks))
-    return fail(h, DSL_ERR_INVALID, "dsl_slab_attach: neighbour rank outside the communicator");
-  if (cap_full < 0 || cap_xonly < 0 || !(width_full >= 0.0f) || !(width >= width_full))
-    return fail(h, DSL_ERR_INVALID, "dsl_slab_attach: bad widths or capacities");
-  if (overlap && !use_tiled(h)) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_attach: the split step needs DSL_MATH_FAST");
-  (void)dsl_slab_detach(h);
-  SlabLink* L = new (std::nothrow) SlabLink();
-  if (!L) return fail(h, DSL_ERR_NOMEM, "dsl_slab_attach: out of host memory");
-  h->link = L;
-  L->comm = comm;
-  L->lo = lo_rank;
-  L->hi = hi_rank;
-  L->width_full = width_full;
-  L->width = width;
-  L->cap_full = cap_full;
-  L->cap_x = cap_xonly;
-  L->max_full = 2 * cap_full;  // room for the re-plan to grow the messages (the same on every rank)
-  L->max_x = 2 * cap_xonly;
-  L->overlap = overlap != 0 && (lo_rank >= 0 || hi_rank >= 0);
-  L->buf_floats = (size_t)(L->max_full + 1) * kRecordPci + (size_t)L->max_x * kRecordX;  // (13-float records once PCISPH runs)
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = dev_alloc(h, &L->send[k], L->buf_floats)) return rc;
-    if (int rc = dev_alloc(h, &L->recv[k], L->buf_floats)) return rc;
-    HIP_TRY(h, hipMemsetAsync(L->send[k], 0, L->buf_floats * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(L->recv[k], 0, L->buf_floats * sizeof(float), h->stream));
-  }
-  if (int rc = dev_alloc(h, &L->dev_words, 4)) return rc;
-  {  // the transfer stream gets the highest priority: a hardware queue of its own (two plain streams may share
-     // one, and then the transfer kernels wait behind the interior force launch they are meant to run under)
-    int least = 0, greatest = 0;
-    HIP_TRY(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(h, hipStreamCreateWithPriority(&L->comm_stream, hipStreamNonBlocking, greatest));
-  }
-  HIP_TRY(h, hipEventCreateWithFlags(&L->ev_pack, hipEventDisableTiming));
-  HIP_TRY(h, hipEventCreateWithFlags(&L->ev_xfer, hipEventDisableTiming));
-  if (L->overlap) {
-    if (int rc = dsl_slab_split(h, width, h->split_margin > 0.0f ? h->split_margin : width)) return rc;
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DSL_OK;
-}
-
-namespace {
-// one fixed-size message per neighbour and direction, all four transfers in one RCCL group
-int link_post(dsl_handle* h, hipStream_t st) {
-  SlabLink& L = *h->link;
-  if (L.lo < 0 && L.hi < 0) return DSL_OK;
-  const size_t n = dsl_slab_message_floats_for(h, L.cap_full, L.cap_x);
-  dsl_comm* comm = L.comm;
-  if (int rc = xfer_group_start(h, comm)) return rc;
-  // (an error between group start and group end must not leave the group open: every later RCCL call of the
-  // process would be queued into it and nothing would ever be sent -- close it, keep the first error)
-  auto body = [&]() -> int {
-    if (L.lo >= 0)
-      if (int rc = xfer_send(h, comm, L.send[0], n, L.lo, st)) return rc;
-    if (L.hi >= 0)
-      if (int rc = xfer_send(h, comm, L.send[1], n, L.hi, st)) return rc;
-    // two messages between the same pair of ranks (two ranks with periodic images, or a rank that is
-    // its own neighbour in a test) are matched in issue order: the peer's LOW band arrives from above
-    const bool same_peer = L.lo >= 0 && L.lo == L.hi;
-    if (same_peer) {
-      if (int rc = xfer_recv(h, comm, L.recv[1], n, L.hi, st)) return rc;
-      if (int rc = xfer_recv(h, comm, L.recv[0], n, L.lo, st)) return rc;
-    } else {
-      if (L.lo >= 0)
-        if (int rc = xfer_recv(h, comm, L.recv[0], n, L.lo, st)) return rc;
-      if (L.hi >= 0)
-        if (int rc = xfer_recv(h, comm, L.recv[1], n, L.hi, st)) return rc;
-    }
-    return DSL_OK;
-  };
-  const int rc = body();
-  if (rc != DSL_OK) {
-    const std::string first = h->err;
-    (void)xfer_group_end(h, comm);
-    h->err = first;
-    return rc;
-  }
-  return xfer_group_end(h, comm);
-}
-
-int link_append(dsl_handle* h) {
-  SlabLink& L = *h->link;
-  if (L.lo < 0 && L.hi < 0) return DSL_OK;
-  if (int rc = slab_append_shifted(h, L.lo >= 0 ? L.recv[0] : nullptr, L.hi >= 0 ? L.recv[1] : nullptr, L.cap_full, L.cap_x,
-                                   L.shift_from_lo, L.shift_from_hi))
-    return rc;
-  L.ghosts_in = true;
-  return DSL_OK;
-}
-
-// the band selection into the link's send buffers, one per neighbour there is
-// (static: this block is inside extern "C", where the compiler exports even an unnamed namespace's functions by name)
-static int link_pack(dsl_handle* h, hipStream_t st, float width, bool from_output) {
-  SlabLink& L = *h->link;
-  return slab_pack_on(h, st, L.width_full, width, from_output, L.lo >= 0 ? L.send[0] : nullptr, L.hi >= 0 ? L.send[1] : nullptr,
-                      L.cap_full, L.cap_x);
-}
-
-// unsplit exchange on the handle's stream: pack, transfer, append
-int link_exchange(dsl_handle* h) {
-  SlabLink& L = *h->link;
-  if (L.lo < 0 && L.hi < 0) return DSL_OK;
-  if (int rc = link_pack(h, h->stream, L.width, false)) return rc;
-  if (int rc = link_post(h, h->stream)) return rc;
-  return link_append(h);
-}
-
-// ---- re-balancing: the slab planes move with the particles (dsl_slab_rebalance) ----
-// where layer plane k lies: the one expression every check and every move uses
-static float balance_plane(const dsl_handle* h, float origin, int k) { return origin + (float)k * h->c.cell; }
-
-// is `x` on a cell plane of the handle's grid along the slab axis (1e-3 cell of slack, as update_split allows)?
-static bool on_cell_plane(const dsl_handle* h, float x) {
-  const float f = (x - h->c.gmin[h->c.slab_axis]) * h->c.inv_cell;
-  return std::fabs(f - std::nearbyint(f)) <= 1.0e-3f;
-}
-
-// the fullest layer next to an interior plane in the last global histogram; -1 before the first look
-static long long balance_adjacent_max(const SlabBalance& B) {
-  if (B.counts.empty()) return -1;
-  long long m = 0;
-  for (int r = 1; r < B.nranks; ++r)
-    for (int k = B.planes[(size_t)r] - 1; k <= B.planes[(size_t)r]; ++k)
-      if (k >= 0 && k < B.n_layers && B.counts[(size_t)k] > m) m = B.counts[(size_t)k];
-  return m;
-}
-
-// owned particles per layer into dev_counts (overwritten), on the handle's stream
-static int layer_counts_on(dsl_handle* h, float origin, int n_layers, int32_t* dev_counts) {
-  HIP_TRY(h, hipMemsetAsync(dev_counts, 0, sizeof(int32_t) * (size_t)n_layers, h->stream));
-  launch_slab_layer_count(h->stream, h->c, launch_n(h), cpos(h), origin, n_layers, dev_counts);
-  HIP_TRY(h, hipGetLastError());
-  return DSL_OK;
-}
-
-// new planes on the host; the particles are not touched.  Between an integrate and the pack that follows it ownership
-// is positional among the live particles (every ghost is NaN): whoever lies outside the new planes leaves as a migrant.
-static void move_planes(dsl_handle* h, float lo, float hi) {
-  h->c.slab_lo = lo;
-  h->c.slab_hi = hi;
-  update_split(h);
-  h->grid_valid = false;  // the owning / band / interior tile lists are made by the neighbour build
-}
-
-// The look: count, one MAX all-reduce over n_layers words (the ranks' histograms are disjoint -- one owner per live
-// particle, planes on layer boundaries -- so the MAX of the non-negative counts is their sum), one host synchronisation,
-// the plan.  A plan that moves a plane is applied by the NEXT step, between its integrate and its pack.
-static int balance_look(dsl_handle* h) {
-  SlabLink& L = *h->link;
-  SlabBalance& B = L.bal;
-  if (int rc = layer_counts_on(h, B.origin, B.n_layers, B.dev_counts)) return rc;
-  if (L.comm && L.comm->nranks > 1)
-    if (int rc = xfer_all_reduce_max(h, L.comm, B.dev_counts, (size_t)B.n_layers, h->stream)) return rc;
-  B.counts.resize((size_t)B.n_layers);
-  HIP_TRY(h, hipMemcpyAsync(B.counts.data(), B.dev_counts, sizeof(int32_t) * (size_t)B.n_layers, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  std::vector<int32_t> next(B.planes.size());
-  const int moved = slab_plan_planes(B.counts.data(), B.n_layers, B.nranks, B.planes.data(), B.plane_min.data(),
-                                     B.plane_max.data(), B.min_layers, next.data());
-  B.planes.swap(next);
-  B.pending = B.pending || moved > 0;
-  B.moves += moved;
-  B.looks++;
-  return DSL_OK;
-}
-
-static void balance_apply(dsl_handle* h) {
-  SlabBalance& B = h->link->bal;
-  B.pending = false;
-  // (a domain end stays where dsl_slab_config put it: -INFINITY / INFINITY, usually)
-  const float lo = B.rank > 0 ? balance_plane(h, B.origin, B.planes[(size_t)B.rank]) : h->c.slab_lo;
-  const float hi = B.rank + 1 < B.nranks ? balance_plane(h, B.origin, B.planes[(size_t)B.rank + 1]) : h->c.slab_hi;
-  move_planes(h, lo, hi);
-}
-
-// every rank learns the largest band counts (and any overflow) seen anywhere since the last
-// re-plan; all ranks switch to the same new message capacities.  Blocking.
-int link_replan(dsl_handle* h) {
-  SlabLink& L = *h->link;
-  int32_t st[4] = {0, 0, 0, 0};
-  if (int rc = dsl_slab_status(h, st, 1)) return rc;
-  if (L.comm && L.comm->nranks > 1) {
-    HIP_TRY(h, hipMemcpyAsync(L.dev_words, st, sizeof(st), hipMemcpyHostToDevice, h->stream));
-    if (int rc = xfer_all_reduce_max(h, L.comm, L.dev_words, 4, h->stream)) return rc;  // (counts: never negative)
-    HIP_TRY(h, hipMemcpyAsync(st, L.dev_words, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  if (st[0] != 0)
-    return fail(h, DSL_ERR_OVERFLOW,
-                "slab exchange overflow: " + std::to_string(st[0]) +
-                    " records did not fit a band message or the particle capacity on some rank; particles were lost -- "
-                    "enlarge cap_full / cap_xonly / dsl_params.capacity");
-  if (st[1] != 0)
-    return fail(h, DSL_ERR_OVERFLOW, "split slab step: a particle outran the margin on some rank (ghosts were missed); enlarge the margin");
-  long long want_full = (long long)(1.15 * st[2]) + 1024;
-  const long long want_x = (long long)(1.15 * st[3]) + 1024;
-  if (L.bal.every > 0) {
-    // a plane that moves sends one cell layer of migrants on top of the h band: room for the fullest layer next to an
-    // interior plane, by the last global histogram (the same numbers on every rank); before the first look there is
-    // none, and the capacity the host attached with -- sized for band + layer -- is kept
-    const long long layer = balance_adjacent_max(L.bal);
-    want_full = layer >= 0 ? want_full + layer : (want_full > L.cap_full ? want_full : L.cap_full);
-  }
-  L.cap_full = (int)(want_full < L.max_full ? want_full : L.max_full);
-  L.cap_x = (int)(want_x < L.max_x ? want_x : L.max_x);
-  return DSL_OK;
-}
-}  // namespace
-
-int dsl_slab_image_shift(dsl_handle* h, float from_lo, float from_hi) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_image_shift: call dsl_slab_attach first");
-  h->link->shift_from_lo = from_lo;
-  h->link->shift_from_hi = from_hi;
-  return DSL_OK;
-}
-
-int dsl_slab_exchange(dsl_handle* h) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_exchange: call dsl_slab_attach first");
-  if (h->split_pending) return fail(h, DSL_ERR_INVALID, "dsl_slab_exchange: a split force pass is in flight");
-  return link_exchange(h);
-}
-
-int dsl_slab_replan(dsl_handle* h) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_replan: call dsl_slab_attach first");
-  return link_replan(h);
-}
-
-int dsl_slab_layer_counts(dsl_handle* h, float origin, int n_layers, int32_t* dev_counts) {
-  CHECK_HANDLE(h);
-  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: no slab configured");
-  if (!dev_counts) return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: null output");
-  if (n_layers < 1 || n_layers > kBalMaxLayers)
-    return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: n_layers must be between 1 and " + std::to_string(kBalMaxLayers));
-  if (!std::isfinite(origin) || !on_cell_plane(h, origin))
-    return fail(h, DSL_ERR_INVALID, "dsl_slab_layer_counts: origin is not on a cell plane of this handle's grid");
-  return layer_counts_on(h, origin, n_layers, dev_counts);
-}
-
-int dsl_slab_move_planes(dsl_handle* h, float lo, float hi) {
-  CHECK_HANDLE(h);
-  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: no slab configured");
-  if (!(lo < hi)) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: empty range");
-  if (h->split_pending) return fail(h, DSL_ERR_INVALID, "dsl_slab_move_planes: a split force pass is in flight");
-  move_planes(h, lo, hi);
-  return DSL_OK;
-}
-
-int dsl_slab_get_planes(dsl_handle* h, float* lo, float* hi) {
-  CHECK_HANDLE_ONLY(h);
-  if (!h->c.n_ptr) return fail(h, DSL_ERR_INVALID, "dsl_slab_get_planes: no slab configured");
-  if (lo) *lo = h->c.slab_lo;
-  if (hi) *hi = h->c.slab_hi;
-  return DSL_OK;
-}
-
-int dsl_slab_rebalance(dsl_handle* h, int every, float origin, int n_layers, const int32_t* planes, const int32_t* plane_min,
-                       const int32_t* plane_max, int min_layers) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance: call dsl_slab_attach first");
-  SlabLink& L = *h->link;
-  SlabBalance& B = L.bal;
-  if (every < 0) return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance: every must be >= 0");
-  if (every == 0) {  // off: no further look (a move the last look planned is still applied by the next step)
-    B.every = 0;
-    return DSL_OK;
-  }
-  const char* who = "dsl_slab_rebalance: ";
-  if (n_layers < 1 || n_layers > kBalMaxLayers)
-    return fail(h, DSL_ERR_INVALID, std::string(who) + "n_layers must be between 1 and " + std::to_string(kBalMaxLayers) +
-                                        " (the count's histogram), got " + std::to_string(n_layers));
-  if (min_layers < 2)
-    return fail(h, DSL_ERR_INVALID, std::string(who) + "min_layers must be >= 2 (a slab thinner than the 2h band would leave "
-                                                       "its neighbour's ghosts to two ranks), got " + std::to_string(min_layers));
-  if (!planes || !plane_min || !plane_max) return fail(h, DSL_ERR_INVALID, std::string(who) + "null planes or bounds");
-  if (!std::isfinite(origin) || !on_cell_plane(h, origin))
-    return fail(h, DSL_ERR_INVALID, std::string(who) + "origin is not on a cell plane of this handle's grid");
-  const int R = L.comm ? L.comm->nranks : 1, rank = L.comm ? L.comm->rank : 0;
-  for (int r = 0; r <= R; ++r) {
-    if (planes[r] < 0 || planes[r] > n_layers || (r > 0 && planes[r] - planes[r - 1] < min_layers))
-      return fail(h, DSL_ERR_INVALID, std::string(who) + "planes must ascend inside [0, n_layers], min_layers apart (plane " +
-                                          std::to_string(r) + ")");
-    if (r > 0 && r < R && !(plane_min[r] <= planes[r] && planes[r] <= plane_max[r]))
-      return fail(h, DSL_ERR_INVALID, std::string(who) + "plane " + std::to_string(r) + " lies outside its own bounds");
-  }
-  const int a = h->c.slab_axis;
-  const float g0 = h->c.gmin[a], g1 = h->c.gmin[a] + (float)h->c.dims[a] * h->c.cell, slack = 1.0e-3f * h->c.cell;
-  for (int side = 0; side < 2; ++side) {
-    const int r = rank + side;
-    const float cur = side == 0 ? h->c.slab_lo : h->c.slab_hi;
-    if (r == 0 || r == R) continue;  // a domain end: never moves
-    if (!(std::fabs(cur - balance_plane(h, origin, planes[r])) <= slack))
-      return fail(h, DSL_ERR_INVALID, std::string(who) + "this rank's " + (side == 0 ? "lower" : "upper") + " plane (" +
-                                          std::to_string(cur) + ") is not origin + planes[" + std::to_string(r) + "] * edge (" +
-                                          std::to_string(balance_plane(h, origin, planes[r])) + ")");
-    const float reach_lo = balance_plane(h, origin, plane_min[r]) - L.width, reach_hi = balance_plane(h, origin, plane_max[r]) + L.width;
-    if (reach_lo < g0 - slack || reach_hi > g1 + slack)
-      return fail(h, DSL_ERR_INVALID, std::string(who) + "plane " + std::to_string(r) + " with its band may reach [" +
-                                          std::to_string(reach_lo) + ", " + std::to_string(reach_hi) + "], this handle's grid covers [" +
-                                          std::to_string(g0) + ", " + std::to_string(g1) + "] along the slab axis");
-  }
-  if (!B.dev_counts)
-    if (int rc = dev_alloc(h, &B.dev_counts, (size_t)kBalMaxLayers)) return rc;
-  B.every = every;
-  B.origin = origin;
-  B.n_layers = n_layers;
-  B.min_layers = min_layers;
-  B.nranks = R;
-  B.rank = rank;
-  B.planes.assign(planes, planes + R + 1);
-  B.plane_min.assign(plane_min, plane_min + R + 1);
-  B.plane_max.assign(plane_max, plane_max + R + 1);
-  B.counts.clear();
-  B.pending = false;
-  B.looks = B.moves = 0;
-  return DSL_OK;
-}
-
-int dsl_slab_rebalance_state(dsl_handle* h, int32_t* planes, int32_t* counts, int64_t* looks, int64_t* moves) {
-  CHECK_HANDLE(h);
-  if (!h->link || h->link->bal.planes.empty())
-    return fail(h, DSL_ERR_INVALID, "dsl_slab_rebalance_state: call dsl_slab_rebalance first");
-  const SlabBalance& B = h->link->bal;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (planes) std::copy(B.planes.begin(), B.planes.end(), planes);
-  if (counts)
-    for (int k = 0; k < B.n_layers; ++k) counts[k] = B.counts.empty() ? 0 : B.counts[(size_t)k];
-  if (looks) *looks = B.looks;
-  if (moves) *moves = B.moves;
-  return DSL_OK;
-}
-
-int dsl_slab_wcsph_step(dsl_handle* h, int nsteps) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_wcsph_step: call dsl_slab_attach first");
-  SlabLink& L = *h->link;
-  const bool alone = L.lo < 0 && L.hi < 0;
-  // (Round 2 could replay the step's kernel segments as hipGraphs: measured 5 % SLOWER than launching its ~20 kernels one
-  // by one -- the host needs 45 us per step for them either way, the GPU 500 us; profiles/r02_slab_graphs_on_off.txt.
-  // Removed in round 4.)
-  for (int s = 0; s < nsteps; ++s) {
-    if (!L.ghosts_in)
-      if (int rc = link_exchange(h)) return rc;  // first step: migrants + 2h ghosts from both neighbours
-    L.ghosts_in = false;
-    // counting sort (drops the previous step's ghosts), densities of owned + ghosts
-    if (int rc = build_grid(h, false)) return rc;
-    if (int rc = density_pass(h)) return rc;
-    if (alone || !L.overlap || L.bal.pending) {
-      // forces and integration of the owned particles (ghosts are marked for removal), band pack, transfer, append
-      // (a rank without neighbours exchanges nothing)
-      if (int rc = force_integrate(h)) return rc;
-      if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set) before the pack decides ownership
-      // re-balancing: the planes of the last look's plan take over here, where every ghost is NaN and the pack that
-      // follows hands over whoever lies outside them.  (Unsplit even with overlap: the band launch would have
-      // integrated, and would pack, the layers of the old planes.)
-      if (L.bal.pending) balance_apply(h);
-      if (int rc = link_exchange(h)) return rc;
-    } else {
-      // band layers first; their pack and the RCCL transfer (side stream) run under the interior launch
-      if (int rc = force_integrate(h, 1)) return rc;
-      if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set) the band layers, in the output half
-      h->split_pending = true;
-      if (int rc = link_pack(h, h->stream, h->split_width, true)) return rc;
-      // the interior launch is queued BEHIND the pack and BEFORE the transfer is posted: the GPU goes straight from
-      // the pack into it, the transfer kernels (side stream, behind the pack's event) join it
-      HIP_TRY(h, hipEventRecord(L.ev_pack, h->stream));
-      h->split_pending = false;
-      if (int rc = force_integrate(h, 2)) return rc;
-      if (int rc = collide_pass(h)) return rc;  // ... the other layers: queued before the append, under the transfer
-      HIP_TRY(h, hipStreamWaitEvent(L.comm_stream, L.ev_pack, 0));
-      if (int rc = link_post(h, L.comm_stream)) return rc;
-      HIP_TRY(h, hipEventRecord(L.ev_xfer, L.comm_stream));
-      HIP_TRY(h, hipStreamWaitEvent(h->stream, L.ev_xfer, 0));
-      if (int rc = link_append(h)) return rc;
-    }
-    h->steps++;
-    L.steps++;
-    if (L.bal.every > 0 && L.steps % L.bal.every == 0)
-      if (int rc = balance_look(h)) return rc;
-    if (!alone && L.steps % L.replan_every == 0)
-      if (int rc = link_replan(h)) return rc;
-  }
-  return DSL_OK;
-}
-
-int dsl_slab_pcisph_step(dsl_handle* h, int nsteps) {
-  CHECK_HANDLE(h);
-  if (!h->link) return fail(h, DSL_ERR_INVALID, "dsl_slab_pcisph_step: call dsl_slab_attach first");
-  if (!h->pci_active) return fail(h, DSL_ERR_INVALID, "dsl_slab_pcisph_step: call dsl_pcisph_begin first");
-  SlabLink& L = *h->link;
-  const bool alone = L.lo < 0 && L.hi < 0;
-  const bool reduce = L.comm && L.comm->nranks > 1;
-  for (int s = 0; s < nsteps; ++s) {
-    if (!L.ghosts_in)
-      if (int rc = link_exchange(h)) return rc;
-    L.ghosts_in = false;
-    h->pci_split_guard = true;
-    if (int rc = pci_begin_step(h)) return rc;
-    for (int it = 0; it < h->prm.pci_max_iters; ++it) {
-      if (int rc = pci_iterate(h)) return rc;
-      // the early-out of pcisph_darwin.go:95-98 is decided by the maximum over all ranks: the error
-      // word holds a non-negative float, whose bits order like an unsigned integer
-      if (reduce)
-        if (int rc = xfer_all_reduce_max(h, L.comm, &h->dstats->pci_cur_err_bits, 1, h->stream)) return rc;
-      if (int rc = pci_check(h)) return rc;
-    }
-    h->pci_split_guard = false;
-    if (int rc = pci_end_step(h)) return rc;  // Update; ghosts are marked for removal
-    if (L.bal.pending) balance_apply(h);      // re-balancing: as in dsl_slab_wcsph_step (migrants carry their predictor state)
-    if (int rc = link_exchange(h)) return rc;
-    L.steps++;
-    if (L.bal.every > 0 && L.steps % L.bal.every == 0)
-      if (int rc = balance_look(h)) return rc;
-    if (!alone && L.steps % L.replan_every == 0)
-      if (int rc = link_replan(h)) return rc;
-  }
   return DSL_OK;
 }
 
@@ -3551,5 +2394,3 @@ int dsl_timing_get(dsl_handle* h, int kid, double* avg_ms, int64_t* launches) {
   if (launches) *launches = h->launches[kid];
   return DSL_OK;
 }
-
-}  // extern "C"

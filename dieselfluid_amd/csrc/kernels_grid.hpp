@@ -608,14 +608,7 @@ __global__ __launch_bounds__(kBlock) void k_pack1(int n, float* __restrict__ sta
 // ---------------------------------------------------------------------------------
 // slab halo: band selection (wave-aggregated append) and record append
 // ---------------------------------------------------------------------------------
-constexpr int kRecord = 7;      // full record: x,y,z,vx,vy,vz,id-bits
-constexpr int kRecordPci = 13;  // ... + the PCISPH predictor state (_pos, _vel) once dsl_pcisph_begin has run
-// position-only record: x,y,z,id-bits.  (The id used to stay behind, 12 bytes per record: the receiver numbered these
-// ghosts itself, so inside a cell they sat in message order instead of id order -- the densities of the ghosts next
-// to them were then summed in another order than a single-domain run sums them, and EXACT slabs were one ulp away
-// from it in a few particles per step.  With the id every cell of every rank is in the single-domain order.)
-constexpr int kRecordX = 4;
-
+// (the record sizes kRecord, kRecordPci, kRecordX: sph_device.hpp -- the slab link sizes its buffers by them)
 // Message layout (floats): header of `rec` words ([0] = full-record count, [1] =
 // position-only count, int bits), cap_full full records of `rec` words (rec = kRecord or
 // kRecordPci), cap_x position-only records.

@@ -83,20 +83,7 @@ __device__ __forceinline__ void sync_lds() {
   __syncthreads();
 }
 
-struct TileGrid {
-  int tnx, tny, tnz, ntiles;
-  // Enumeration order of the tile list (k_tile_list): boxes of bx x by x bz tiles, the boxes x-fastest and the
-  // tiles of a box x-fastest -- NOT the tile grid's own linear order.  The persistent kernels deal the list to
-  // the 8 XCDs in groups of 128 consecutive entries (TileWalk), so with 128-tile boxes every XCD works on one
-  // compact 3-D box of tiles at a time and the halo rows its tiles share are served by that XCD's L2: the
-  // tiles of a box fetch 1.3 x its particles from HBM, where 128 tiles of the linear order (a 32 x 4 x 1 sheet)
-  // fetch 1.7 x and share nothing with the sheets above and below.  bx = 0: linear order.
-  int bx, by, bz, nbx, nby, nlist;  // nlist = list threads = boxes * box size
-  // cell layers a tile owns along z: kTB, or 3 for the skin step (kernels_skin.hpp) -- its cells are h (1 + s) wide, and
-  // 4 x 4 x 3 of them hold the ~512 targets and ~1900 staged records that 4 x 4 x 4 cells of edge h hold: the tile
-  // tables keep their shape (interior rows 12..15 and staged rows 30..35 are simply empty)
-  int tbz;
-};
+// (struct TileGrid: sph_device.hpp -- the host's handle holds one)
 __device__ __forceinline__ int tile_of_list_thread(const TileGrid& tg, int t) {
   if (tg.bx == 0) return t < tg.ntiles ? t : -1;
   const int per = tg.bx * tg.by * tg.bz;

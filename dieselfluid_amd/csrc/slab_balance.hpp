@@ -1,6 +1,6 @@
 // slab_balance.hpp -- the launcher of the slab re-balancing count (dsl_slab_layer_counts, the look of
 // dsl_slab_rebalance): owned particles per cell layer along the slab axis.  The kernel is compiled in a translation
-// unit of its own, slab_balance.hip; dslsph.hip includes this header only.
+// unit of its own, slab_balance.hip; slab_link.hip includes this header only.
 #pragma once
 
 #include "sph_device.hpp"

@@ -280,6 +280,30 @@ __device__ __forceinline__ bool pci_query_escaped(const DevConsts& c, float qx, 
 // The same rule, on a particle's cell before the step, tells the band pack which slots the first
 // launch has integrated.
 constexpr int kTB = 4;  // tile edge in cells (kernels_tiled.hpp)
+// the tile grid over the cell grid (kernels_tiled.hpp)
+struct TileGrid {
+  int tnx, tny, tnz, ntiles;
+  // Enumeration order of the tile list (k_tile_list): boxes of bx x by x bz tiles, the boxes x-fastest and the
+  // tiles of a box x-fastest -- NOT the tile grid's own linear order.  The persistent kernels deal the list to
+  // the 8 XCDs in groups of 128 consecutive entries (TileWalk), so with 128-tile boxes every XCD works on one
+  // compact 3-D box of tiles at a time and the halo rows its tiles share are served by that XCD's L2: the
+  // tiles of a box fetch 1.3 x its particles from HBM, where 128 tiles of the linear order (a 32 x 4 x 1 sheet)
+  // fetch 1.7 x and share nothing with the sheets above and below.  bx = 0: linear order.
+  int bx, by, bz, nbx, nby, nlist;  // nlist = list threads = boxes * box size
+  // cell layers a tile owns along z: kTB, or 3 for the skin step (kernels_skin.hpp) -- its cells are h (1 + s) wide, and
+  // 4 x 4 x 3 of them hold the ~512 targets and ~1900 staged records that 4 x 4 x 4 cells of edge h hold: the tile
+  // tables keep their shape (interior rows 12..15 and staged rows 30..35 are simply empty)
+  int tbz;
+};
+
+// slab halo messages (kernels_grid.hpp: band selection and record append), in floats per record
+constexpr int kRecord = 7;      // full record: x,y,z,vx,vy,vz,id-bits
+constexpr int kRecordPci = 13;  // ... + the PCISPH predictor state (_pos, _vel) once dsl_pcisph_begin has run
+// position-only record: x,y,z,id-bits.  (The id used to stay behind, 12 bytes per record: the receiver numbered these
+// ghosts itself, so inside a cell they sat in message order instead of id order -- the densities of the ghosts next
+// to them were then summed in another order than a single-domain run sums them, and EXACT slabs were one ulp away
+// from it in a few particles per step.  With the id every cell of every rank is in the single-domain order.)
+constexpr int kRecordX = 4;
 __device__ __forceinline__ bool slab_band_cell(const DevConsts& c, int ca) { return ca < c.split_cl || ca >= c.split_ch; }
 __device__ __forceinline__ int slab_axis_cell(const DevConsts& c, float x, float y, float z) {
   const int a = c.slab_axis;

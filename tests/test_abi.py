@@ -27,6 +27,25 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert set(declared) == set(_lib.EXPORTS), "ctypes binding table drifted from the header"
 
 
+def test_library_exports_no_plain_name_beyond_the_header():
+    """A host program shares the process's global C namespace with this library: besides the C++-mangled names (_Z...)
+    and the HIP runtime's registration symbols (__hip_...), the dynamic symbol table defines exactly the dsl_* functions
+    include/dslsph.h declares -- no helper of the library's own under a plain name a host might use itself."""
+    import subprocess
+    from dieselfluid_amd import _lib
+    _lib.build_library()
+    # (ROCm's LLVM, next to the compiler that built the library: this ROCm ships llvm-readelf, not llvm-nm)
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "--wide", _lib.library_path()], check=True,
+                         capture_output=True, text=True).stdout
+    # "   Num:    Value          Size Type    Bind   Vis       Ndx Name": defined = the section index is not UND
+    rows = [line.split() for line in out.splitlines() if re.match(r"\s*\d+:", line)]
+    names = {r[7].split("@")[0] for r in rows if len(r) >= 8 and r[6] != "UND" and r[4] in ("GLOBAL", "WEAK")}
+    plain = {n for n in names if not n.startswith(("_Z", "__hip_"))}
+    assert len(names) > len(plain) >= 25
+    declared = set(_declared_symbols())
+    assert plain == declared, (sorted(plain - declared), sorted(declared - plain))
+
+
 def test_params_struct_layout_matches_header():
     from dieselfluid_amd import _lib, engine
     p = engine.reference_params(16)
