@@ -414,9 +414,26 @@ __global__ __launch_bounds__(kLBlock, 4) void k_list_build(DevConsts c, TileGrid
 // ---------------------------------------------------------------------------------
 // staging of a tile for the list walks: lane t owns quad t % kLQuads of staged row t / kLQuads (and every kLQuads-th
 // quad behind it: wide cells make long rows).  load4(g, float4 out[NF]) / store(record, float rec[NF], real)
+// DEALT (kernels_tiled.hpp, "DEALT staging"): lane t takes quad t of the tile, whichever row it falls into -- one
+// quad per lane, every load of the tile in flight before the first wait; a tile of more than kLBlock quads takes
+// further passes (the loop's trip count is the block's, a scalar).
 // ---------------------------------------------------------------------------------
-template <int NF, class Load4, class Store>
+template <int NF, bool DEALT, class Load4, class Store>
 __device__ __forceinline__ void stage_tile(const TileMeta& m, Load4&& load4, Store&& store) {
+  if constexpr (DEALT) {
+    const int nq = __builtin_amdgcn_readfirstlane((int)m.qprefix[kTRows]);
+    // (the first pass stands outside the loop: across a back edge the loads would wait for whatever is in flight --
+    // the walks' first list chunks)
+    auto pass = [&](int base) {
+      StageRegs<NF> sr;
+      const StageWhere w = stage_issue_dealt<NF>(m, load4, sr, base + (int)threadIdx.x, nq);
+      stage_commit_dealt<NF>(sr, w, store);
+    };
+    pass(0);
+    for (int base = kLBlock; base < nq; base += kLBlock) pass(base);
+    stage_pads<NF>(m, store, threadIdx.x);
+    return;
+  }
   const int t = threadIdx.x, r = t / kLQuads, k = t - r * kLQuads;
   if (r >= kTRows) return;
   const int len = m.row_len[r], gs = m.row_gs[r], ls = m.row_lds[r];
@@ -537,7 +554,7 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
       q0 = load_chunk(lists, tt0.g);
       q1 = load_chunk(lists, (size_t)lstride + tt0.g);
     }
-    if (staged) stage_tile<3>(m, LoadPos4{p}, StoreTileRecord(A, m, c.inv_hh));
+    if (staged) stage_tile<3, (kStageDealt & 1) != 0>(m, LoadPos4{p}, StoreTileRecord(A, m, c.inv_hh));
     if (have) tile_meta_store(metas[cur ^ 1], table_word);
     sync_lds();
     for_each_target<true, kLBlock>(ntarg, tid, tperm, [&](auto shared_c, int t, int sub, int k) {
@@ -686,7 +703,7 @@ __global__ __launch_bounds__(kLBlock, 4) void k_force_list(DevConsts c, TileGrid
       q1 = load_chunk(lists, (size_t)lstride + tt0.g);
     }
     if (staged)
-      stage_tile<8>(
+      stage_tile<8, (kStageDealt & 2) != 0>(
           m,
           [&](int gg, float4* o) {
             o[0] = load4u(pin.x + gg);

@@ -63,14 +63,18 @@ struct TileMeta {
   // k_density_pair: prefix, over the 16 interior rows, of the rows' PAIR SLOTS (a slot = two targets of one cell, or a
   // cell's odd one out: sum over the row's four cells of (count + 1) / 2)
   int pprefix[kTB * kTB + 1];
-  int pad2_[3];                   // 360 ints: a whole number of 16-byte pieces
+  // dealt staging (stage_issue_dealt): prefix, over the 36 staged rows, of the rows' QUADS ((row_len + 3) / 4), the
+  // tile's total in [kTRows]; 16 bits each -- a staged tile holds at most kTCap records.  One entry of padding:
+  // 376 ints, a whole number of 16-byte pieces
+  unsigned short qprefix[kTRows + 2];
 };
 // A tile's table is built ONCE per neighbour build, by k_tile_desc, into a global array of these
 // (one per non-empty tile, in the order of tile list 0); the sweeping kernels copy it into LDS, one
 // dword per lane, one tile ahead of its use.  (Each kernel used to derive it again for every tile it
 // visited -- seven dependent loads per row, a scan and two more barriers in front of every staging.)
-constexpr int kMetaInts = 360;
+constexpr int kMetaInts = 376;
 static_assert(sizeof(TileMeta) == kMetaInts * sizeof(int), "TileMeta is copied as kMetaInts dwords");
+static_assert(kMetaInts % 4 == 0 && kMetaInts <= kTBlock, "one dword per lane of a 512-thread block, two of a 256-thread one");
 
 // __syncthreads() with the wave's own LDS traffic drained first, stated explicitly.  hipcc leaves the
 // `s_waitcnt lgkmcnt(0)` in front of an s_barrier to its waitcnt pass, and at the head of the double-buffered loops
@@ -300,9 +304,14 @@ __global__ __launch_bounds__(kWave) void k_tile_desc(DevConsts c, TileGrid tg, c
       for (int k = 1; k <= kTB; ++k) pv += (q.s[k + 1] - q.s[k] + 1) >> 1;
     }
     const int pinc = wave_inclusive_scan(pv);
+    // quads of four records: what the dealt staging hands out to lanes (a tile beyond the LDS budget is never staged:
+    // its counts may not fit their 16 bits)
+    const int qv = row ? (len + 3) >> 2 : 0;
+    const int qinc = wave_inclusive_scan(qv);
     if (row) {
       out->row_gs[lane] = r.s[0];
       out->row_len[lane] = len;
+      out->qprefix[lane] = (unsigned short)(qinc - qv);
       const int lds0 = inc - v;
       out->row_lds[lane] = lds0;
 #pragma unroll
@@ -331,6 +340,8 @@ __global__ __launch_bounds__(kWave) void k_tile_desc(DevConsts c, TileGrid tg, c
         out->overflow = (inc > lds_cap || tinc > 0xffff) ? 1 : 0;
         out->tprefix[kTB * kTB] = tinc;
         out->pprefix[kTB * kTB] = pinc;
+        out->qprefix[kTRows] = (unsigned short)qinc;
+        out->qprefix[kTRows + 1] = 0;
         out->tile = tile;
         out->centre[0] = __float_as_int(c.gmin[0] + ((tile % tg.tnx) * kTB + 0.5f * kTB) * c.cell);
         out->centre[1] = __float_as_int(c.gmin[1] + (((tile / tg.tnx) % tg.tny) * kTB + 0.5f * kTB) * c.cell);
@@ -723,6 +734,72 @@ __device__ __forceinline__ bool stage_rows(const TileMeta& m, Load4&& load4, Loa
   return true;
 }
 
+// DEALT staging (the skin step's tile kernels: k_density_list, k_force_list, k_density_pair<.., WIDE>).  Cells
+// h (1 + s) wide make rows of 48-52, 72-78 or 108-117 records where the plain step's lattice rows hold 48: fourteen
+// quads per row cover the first kind only, and four tiles in five took a second dependent round trip (a third of them a
+// third; the pair stager fetched the rest record by record) while 84 lanes of rows that are not there, and most lanes
+// of the later passes, idled.  Here the tile's quads -- TileMeta::qprefix, at most ~495 on the lattice -- are dealt to
+// lanes in order: lane t takes quad t - qprefix[r] of the row r it falls into, so every load of the tile is issued
+// before the first wait.  A tile of more quads than the block has quad slots takes further passes of the same
+// dealing.  Records, LDS offsets, pad records and the over-read of up to three elements are stage_issue /
+// stage_commit's: only which lane moves which quad differs.
+// DSL_STAGE_DEALT (build macro, A/B): bit 0 k_density_list, bit 1 k_force_list, bit 2 the wide sweep; 0 = the old
+// dealing everywhere.  The plain step's kernels keep kQuadsPerRow: their lattice rows fit one pass, and the EXACT
+// kernels' stage_values_ok relies on the lane -> quad rule.  (They could take the dealt form through the same three
+// functions -- the table carries qprefix for every tile -- with stage_values_ok told the lane's `where`.)
+#ifndef DSL_STAGE_DEALT
+#define DSL_STAGE_DEALT 7
+#endif
+constexpr int kStageDealt = DSL_STAGE_DEALT;
+// the staged row of quad t < qprefix[kTRows]: the last row whose first quad is at or before t (rows without quads
+// in front of it share its prefix), counted in two rounds of five independent reads
+__device__ __forceinline__ int tile_quad_row(const TileMeta& m, int t) {
+  int r0 = 0;
+#pragma unroll
+  for (int i = 1; i < 6; ++i) r0 += (t >= (int)m.qprefix[6 * i]) ? 6 : 0;
+  int r = r0;
+#pragma unroll
+  for (int i = 1; i < 6; ++i) r += (t >= (int)m.qprefix[r0 + i]) ? 1 : 0;
+  return r;
+}
+// issue: the loads of quad t of the tile (nq: its quads; a lane beyond them loads nothing).  Returns where the quad's
+// records go: the first LDS record and how many of the four are the row's (0: nothing to commit).
+struct StageWhere {
+  int slot, n;
+};
+template <int NF, class Load4>
+__device__ __forceinline__ StageWhere stage_issue_dealt(const TileMeta& m, Load4&& load4, StageRegs<NF>& sr, int t, int nq) {
+  if (t >= nq) return StageWhere{0, 0};
+  const int r = tile_quad_row(m, t), k = t - (int)m.qprefix[r];
+  load4(m.row_gs[r] + 4 * k, sr.v);
+  return StageWhere{m.row_lds[r] + 4 * k, m.row_len[r] - 4 * k};
+}
+template <int NF, class Store>
+__device__ __forceinline__ void stage_commit_dealt(const StageRegs<NF>& sr, const StageWhere& w, Store&& store) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (i < w.n) {
+      float rec[NF];
+#pragma unroll
+      for (int a = 0; a < NF; ++a) rec[a] = f4_at(sr.v[a], i);
+      store(w.slot + i, rec, true);
+    }
+  }
+}
+// the pad records behind every staged row, by stage_commit's rule: quad slot vt = row * kQuadsPerRow + k writes pad k
+template <int NF, class Store>
+__device__ __forceinline__ void stage_pads(const TileMeta& m, Store&& store, int vt) {
+  const int r = vt / kQuadsPerRow, k = vt - r * kQuadsPerRow;
+  if (r >= kTRows) return;
+  const int end = m.row_lds[r] + m.row_len[r];
+  if (k < m.row_lds[r + 1] - end) {
+    float rec[NF];
+#pragma unroll
+    for (int a = 0; a < NF; ++a) rec[a] = 0.0f;
+    store(end + k, rec, false);
+  }
+}
+
 // Which instantiation of the tiled kernels sweeps this neighbour build: the one that shares short
 // passes out (SHARE) when more than one tile in twelve has a short last pass, else the plain one.  The
 // host launches BOTH; each reads the tile statistics k_tile_list left on the device and the one that is
@@ -987,7 +1064,8 @@ __device__ __forceinline__ void sweep_tiles_double_buffered(TileFeed& feed, cons
 // The tile loop of the 256-thread pair kernels (k_density_pair, k_pci_density_qpair; kPBlock, below): one image, two
 // tables, the next tile's table requested ahead of the staging loads.  A tile that fits is staged as tile_records into A;
 // then body(table, overflow) sweeps it -- or, for a tile beyond the LDS budget, does without the image.
-template <int BLOCK, class Body>
+// DEALT: the tile's quads dealt to the lanes in order (stage_issue_dealt), two per lane and pass.
+template <int BLOCK, bool DEALT = false, class Body>
 __device__ __forceinline__ void sweep_tiles_pair(const DevConsts& c, TileFeed& feed, const int* desc, TileMeta* metas,
                                                  float4* A, const CSoa3& p, Body&& body) {
   const int tid = threadIdx.x;
@@ -1025,12 +1103,29 @@ __device__ __forceinline__ void sweep_tiles_pair(const DevConsts& c, TileFeed& f
     const bool ovf = m.overflow != 0;
     if (!ovf) {
       const StoreTileRecord store(A, m, c.inv_hh);
-      // 36 rows x 14 quads = 504 quad slots on 256 lanes: two per lane, all six loads in flight together
-      StageRegs<3> sr0, sr1;
-      stage_issue<3>(m, load4, sr0, tid);
-      stage_issue<3>(m, load4, sr1, tid + BLOCK);
-      stage_commit<3>(m, sr0, load1, store, tid);
-      stage_commit<3>(m, sr1, load1, store, tid + BLOCK);
+      if constexpr (DEALT) {
+        // two quads per lane and pass, all six loads in flight together; ~495 quads at most on the lattice: one pass
+        const int nq = __builtin_amdgcn_readfirstlane((int)m.qprefix[kTRows]);
+        // (the first pass stands outside the loop: across a back edge the loads would wait for whatever is in flight)
+        auto pass = [&](int base) {
+          StageRegs<3> sr0, sr1;
+          const StageWhere w0 = stage_issue_dealt<3>(m, load4, sr0, base + tid, nq);
+          const StageWhere w1 = stage_issue_dealt<3>(m, load4, sr1, base + tid + BLOCK, nq);
+          stage_commit_dealt<3>(sr0, w0, store);
+          stage_commit_dealt<3>(sr1, w1, store);
+        };
+        pass(0);
+        for (int base = 2 * BLOCK; base < nq; base += 2 * BLOCK) pass(base);
+        stage_pads<3>(m, store, tid);
+        stage_pads<3>(m, store, tid + BLOCK);
+      } else {
+        // 36 rows x 14 quads = 504 quad slots on 256 lanes: two per lane, all six loads in flight together
+        StageRegs<3> sr0, sr1;
+        stage_issue<3>(m, load4, sr0, tid);
+        stage_issue<3>(m, load4, sr1, tid + BLOCK);
+        stage_commit<3>(m, sr0, load1, store, tid);
+        stage_commit<3>(m, sr1, load1, store, tid + BLOCK);
+      }
     }
     if (have) meta_store(metas[cur ^ 1], tw);
     sync_lds();
@@ -1461,7 +1556,7 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
   // targets more or less than a block -- and saves a launch that would only find out it is not wanted)
   if (!WIDE && c.slab_axis < 0 && share_wanted(n_tiles) != SHARE) return;
   TileFeed feed(desc_of, *n_tiles);
-  sweep_tiles_pair<kPBlock>(c, feed, desc, metas, A, p, [&](const TileMeta& m, bool ovf) {
+  sweep_tiles_pair<kPBlock, WIDE && (kStageDealt & 4) != 0>(c, feed, desc, metas, A, p, [&](const TileMeta& m, bool ovf) {
     if (ovf) {
       // A tile beyond the LDS budget: its targets one per lane, by the target prefix alone, the grid's 27 cells from
       // global memory.  (Not by pair slots: a tile table packs its in-row cell boundaries into 16 bits -- TileMeta::trow
