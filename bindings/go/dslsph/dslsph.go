@@ -156,6 +156,24 @@ func (e *Engine) Interpolate(scalarBuffer C.int, positions []float32) ([]float32
 		(*C.float)(unsafe.Pointer(&out[0]))))
 }
 
+// InterpolateGrid: Interpolate at every point origin + step * (i, j, k) of a regular lattice (grid.Grid.GridPosition),
+// x fastest: voxel (i, j, k) at (k*dims[1]+j)*dims[0]+i.  devOut (device memory, may be nil) is written asynchronously on
+// the engine's stream; without it the values come back in a host slice.
+func (e *Engine) InterpolateGrid(scalarBuffer C.int, origin, step [3]float32, dims [3]int32, devOut unsafe.Pointer) ([]float32, error) {
+	var out []float32
+	var host *C.float
+	if devOut == nil {
+		n := 1 // (dims the library refuses: one float, so that the refusal is the library's)
+		if dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && int64(dims[0])*int64(dims[1])*int64(dims[2]) <= 1<<30 {
+			n = int(dims[0]) * int(dims[1]) * int(dims[2])
+		}
+		out = make([]float32, n)
+		host = (*C.float)(unsafe.Pointer(&out[0]))
+	}
+	return out, e.ck(C.dsl_field_volume(e.h, scalarBuffer, (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])),
+		(*C.int32_t)(unsafe.Pointer(&dims[0])), (*C.float)(devOut), host))
+}
+
 // ---- render hand-off without the per-step full read-back (pcisph_gpu_darwin.go:276-282) ----
 
 // DownloadDecimated: every stride-th particle of positions / velocities.

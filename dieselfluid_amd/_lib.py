@@ -103,6 +103,7 @@ EXPORTS = {
     "dsl_field_curl": (C.c_int, [_vp, C.c_int, _fp, C.c_size_t]),
     "dsl_field_laplacian": (C.c_int, [_vp, C.c_int, _fp, C.c_size_t]),
     "dsl_field_interpolate": (C.c_int, [_vp, C.c_int, _fp, C.c_size_t, _fp]),
+    "dsl_field_volume": (C.c_int, [_vp, C.c_int, _fp, _fp, _ip, _vp, _fp]),
     "dsl_wcsph_step": (C.c_int, [_vp, C.c_int]),
     "dsl_pcisph_begin": (C.c_int, [_vp]),
     "dsl_pcisph_step": (C.c_int, [_vp, C.c_int]),

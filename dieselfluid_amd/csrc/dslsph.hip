@@ -230,10 +230,14 @@ int drain_timing(dsl_handle* h) {
   return DSL_OK;
 }
 
+}  // namespace
+namespace dsl {
 Neigh neigh(const dsl_handle* h) {
   if (h->lsh) return Neigh{h->cell_start, h->lsh_samples, h->hashv, h->lsh_bits, h->prm.lsh_buckets};
   return Neigh{h->cell_start, nullptr, nullptr, 0, 0};
 }
+}  // namespace dsl
+namespace {
 
 // forces are kept implicit (== force_reset) after Update until a pass needs the array
 int materialise_forces(dsl_handle* h) {
@@ -415,10 +419,10 @@ int build_grid(dsl_handle* h, bool carry_derived) {
   }
   return DSL_OK;
 }
-}  // namespace dsl
-namespace {
 
 int ensure_grid(dsl_handle* h) { return h->grid_valid ? DSL_OK : build_grid(h, true); }
+}  // namespace dsl
+namespace {
 
 // A runtime switch becomes a template argument: `f` is a generic lambda and reads its flag as decltype(flag)::value.
 // Nested calls give several flags; which combinations get a kernel is written as `if constexpr` at the launch.
@@ -770,6 +774,8 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->col_hits);
   (void)hipFree(h->col_query);
   col_index_free(h);
+  (void)hipFree(h->vol_stage);
+  (void)hipFree(h->vol_ctr);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -926,7 +932,7 @@ int dsl_create(const dsl_params* params, int device, dsl_handle** out) {
       (rc = dev_alloc(h, &h->cell_start, (size_t)h->ncell_pad)) ||
       (rc = dev_alloc(h, &h->block_sums, (size_t)h->nscan)) || (rc = dev_alloc(h, &h->stage, n * 3)) ||
       (rc = dev_alloc(h, &h->dstats, 1)) || (rc = dev_alloc(h, &h->dcounter, 8)) || (rc = dev_alloc(h, &h->dn, 16)) ||
-      (rc = dev_alloc(h, &h->walk_ctr, 256)) ||
+      (rc = dev_alloc(h, &h->walk_ctr, 256)) || (rc = dev_alloc(h, &h->vol_ctr, 4)) ||
       (rc = dev_alloc(h, &h->pack_counts, (size_t)4 * ((n + kPackChunk - 1) / kPackChunk))))
     return bail(rc);
   // the sort keeps these two clean between builds (k_scan_apply, k_tile_list)
@@ -1684,6 +1690,7 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
       h->pci_rows_live = false;
       return DSL_OK;
     case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
+    case DSL_OPT_VOLUME_BRICKS: h->vol_bricks = value != 0.0; return DSL_OK;
     case DSL_OPT_COLLIDE_SLAB:
       if (value == 0.0 && h->col_slab && h->c.n_ptr && h->col_tri > 0)
         return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_SLAB cannot go back to 0 while a slab handle holds a "
@@ -1773,6 +1780,11 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
       *value = (double)ctr[option == DSL_OPT_COLLIDE_VISITS ? 0 : 1];
       return DSL_OK;
     }
+    case DSL_OPT_VOLUME_BRICKS: *value = h->vol_bricks ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_VOLUME_LDS_BRICKS: return volume_brick_count(h, 0, value);  // (blocking: the kernel counts on the device)
+    case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
+    case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);
+    case DSL_OPT_VOLUME_STAGED_RECORDS: return volume_brick_count(h, 3, value);
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }

@@ -5,6 +5,7 @@
 //   dslsph.hip         the engine: every kernel launch of the kernel headers, the passes, the single-GPU step drivers
 //   collider_host.hip  the collider's host side (the kernels are in collide.hip, collide_index.hip, collide_slab.hip)
 //   slab_link.hip      multi-GPU: communicator, slab link, re-balancing, the native slab step drivers
+//   volume.hip         field volumes: dsl_field_volume and its two kernels (the one host unit with kernels of its own)
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -169,6 +170,13 @@ struct dsl_handle {
   bool col_slab = false;
   int col_stage = 0;
   bool col_step_zeroed = false;
+  // field volumes (volume.hip; dsl_field_volume).  vol_stage: the library's own output array of a host_out-only call (grows on
+  // demand); vol_ctr: LDS / fallback / empty bricks and staged records of the last brick launch; vol_last_bricks: the last call ran the brick form
+  float* vol_stage = nullptr;
+  size_t vol_stage_count = 0;
+  unsigned long long* vol_ctr = nullptr;
+  bool vol_bricks = true;  // DSL_OPT_VOLUME_BRICKS (the measured choice: DESIGN.md 4.3)
+  bool vol_last_bricks = false;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -264,6 +272,8 @@ inline Bnd bnd_of(const dsl_handle* h) { return Bnd{h->nb > 0 ? h->ids[h->cur_id
 
 // ---- defined in dslsph.hip (every one launches kernels of the kernel headers, or sits next to those that do) ----
 int build_grid(dsl_handle* h, bool carry_derived);
+int ensure_grid(dsl_handle* h);  // the neighbour table of the current positions: built if it is not there
+Neigh neigh(const dsl_handle* h);
 bool use_tiled(const dsl_handle* h);
 int density_pass(dsl_handle* h);
 int force_integrate(dsl_handle* h, int part = 0);
@@ -281,5 +291,8 @@ int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const float* 
 void col_index_free(dsl_handle* h);
 int col_index_update(dsl_handle* h, bool on, float edge_req);
 int collide_pass(dsl_handle* h);
+
+// ---- defined in volume.hip ----
+int volume_brick_count(dsl_handle* h, int which, double* value);  // DSL_OPT_VOLUME_LDS_BRICKS (0), _FALLBACK_BRICKS, _EMPTY_BRICKS, _STAGED_RECORDS (3)
 
 }  // namespace dsl

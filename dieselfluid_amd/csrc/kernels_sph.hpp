@@ -471,12 +471,6 @@ __global__ __launch_bounds__(kBlock) void k_field_div_curl(DevConsts c, Neigh nb
   }
 }
 
-template <bool FAST>
-__device__ __forceinline__ float scalar_field(const DevConsts& c, int field, const float* __restrict__ rho, int j) {
-  const float d = rho[j];
-  return field == 1 ? tait_eos<FAST>(c, d, c.eos_d0_grad) : d;
-}
-
 // Laplacian (sph_field.go:230-248): sum_j m ((f_j - f_i)/rho_j) O2D(r)
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void k_field_laplacian(DevConsts c, Neigh nb, Bnd bnd, CSoa3 p,

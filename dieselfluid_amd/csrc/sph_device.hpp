@@ -246,6 +246,13 @@ __device__ __forceinline__ float tait_eos(const DevConsts& c, float x, float d0)
   return y + 0.0f;
 }
 
+// the scalar fields of the field operators (field_types.go:39-42): 0 the density, 1 PressureField.Value = TaitEos(rho, 87.0, 0)
+template <bool FAST>
+__device__ __forceinline__ float scalar_field(const DevConsts& c, int field, const float* __restrict__ rho, int j) {
+  const float d = rho[j];
+  return field == 1 ? tait_eos<FAST>(c, d, c.eos_d0_grad) : d;
+}
+
 // Cell coordinate rule (DESIGN.md "grid"): floor((p-gmin)*inv_cell) clamped; NaN -> 0.
 __device__ __forceinline__ int cell_coord(float p, float gmin, float inv_cell, int dim) {
   float f = floorf((p - gmin) * inv_cell);

@@ -21,7 +21,7 @@ _COMPS = {0: 3, 1: 3, 2: 3, 3: 1, 4: 1, 5: 3, 6: 3}
 KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
-    "neigh_lists": 13, "collide": 14,
+    "neigh_lists": 13, "collide": 14, "volume": 15,
 }
 
 
@@ -512,6 +512,22 @@ class SPHEngine:
         self._ck(self._L.dsl_field_interpolate(self._h, BUF[scalar], _fp(q), q.shape[0], _fp(out)))
         return out
 
+    def field_volume(self, origin, step, dims, scalar: str = "densities", dev_out=None):
+        """field_interpolate at every point of the lattice origin + step * (i, j, k) (scenes.volume_points), evaluated on the
+        device: an ndarray of shape (nz, ny, nx), or None with `dev_out` -- a device pointer to nx * ny * nz floats, written
+        asynchronously on the engine's stream.  `step` is one number or three."""
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float32), (3,)))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(step, dtype=np.float32), (3,)))
+        d = np.ascontiguousarray(dims, dtype=np.int32).reshape(3)
+        ip = d.ctypes.data_as(C.POINTER(C.c_int32))
+        if dev_out is not None:
+            self._ck(self._L.dsl_field_volume(self._h, BUF[scalar], _fp(o), _fp(s), ip, C.c_void_p(dev_out), None))
+            return None
+        n = int(d[0]) * int(d[1]) * int(d[2])
+        out = np.empty(n if d.min() >= 1 and n <= 1 << 30 else 1, dtype=np.float32)  # (dims the library refuses: _ck raises)
+        self._ck(self._L.dsl_field_volume(self._h, BUF[scalar], _fp(o), _fp(s), ip, None, _fp(out)))
+        return out.reshape(int(d[2]), int(d[1]), int(d[0]))
+
     # -- solver drivers -----------------------------------------------------------
     def wcsph_step(self, nsteps: int = 1):
         self._ck(self._L.dsl_wcsph_step(self._h, int(nsteps)))
@@ -544,7 +560,9 @@ class SPHEngine:
                "pci_qpair": 21, "pci_qrows": 22, "pci_qincr": 23, "list_build": 24, "grid_oversub": 25, "tile_queue": 26,
                "collider_triangles": 32, "collide_hits": 33, "collide_cull": 34,
                "collide_index": 35, "collide_index_edge": 36, "collide_index_cells": 37, "collide_index_entries": 38,
-               "collide_visits": 39, "collide_full_waves": 40, "collide_slab": 41}
+               "collide_visits": 39, "collide_full_waves": 40, "collide_slab": 41,
+               "volume_bricks": 48, "volume_lds_bricks": 49, "volume_fallback_bricks": 50,
+               "volume_empty_bricks": 51, "volume_staged_records": 52}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

@@ -31,6 +31,17 @@ def lattice_positions(n3: int, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
     return (minb[None, :] + (step[None, :] * ijk).astype(f32)).astype(f32)
 
 
+def volume_points(origin, step, dims) -> np.ndarray:
+    """(nx * ny * nz, 3) float32: the voxel coordinates of SPHEngine.field_volume, in its output order (x fastest).  Voxel
+    (i, j, k) lies at origin[a] + step[a] * float32(idx[a]) per axis: one float32 multiplication, one float32 addition
+    (grid.Grid.GridPosition, point-grid.go:59-63) -- the library's rule, bit for bit.  `step` is one number or three."""
+    o = np.broadcast_to(np.asarray(origin, dtype=f32), (3,))
+    s = np.broadcast_to(np.asarray(step, dtype=f32), (3,))
+    ax = [(o[a] + (s[a] * np.arange(int(dims[a])).astype(f32)).astype(f32)).astype(f32) for a in range(3)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.stack([x, y, z], axis=-1).reshape(-1, 3)
+
+
 def reference_scene(n3: int, grid_half_extent: float = 4.0):
     """(params, positions) for sph.Init(1.0, {0,0,0}, nil, n3, pci) in grid mode."""
     p = reference_params(n3)

@@ -151,7 +151,8 @@ enum {
   DSL_K_TILE_LIST = 12, /* non-empty 4x4x4-cell tiles for the LDS-tiled kernels */
   DSL_K_NEIGH_LISTS = 13, /* skin step: wide candidate sweep + neighbour lists (rebuild steps only) */
   DSL_K_COLLIDE = 14,     /* triangle-mesh collider: query + response (only while a mesh is set) */
-  DSL_K_COUNT = 15
+  DSL_K_VOLUME = 15,      /* dsl_field_volume: the lattice sweep, either form */
+  DSL_K_COUNT = 16
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -236,6 +237,31 @@ int dsl_field_curl(dsl_handle *h, int tensor_buffer, float *host_out, size_t cou
 int dsl_field_laplacian(dsl_handle *h, int scalar_buffer, float *host_out, size_t count);    /* Laplacian   :230-248, N   */
 int dsl_field_interpolate(dsl_handle *h, int scalar_buffer, const float *host_positions,     /* Interpolate :124-135      */
                           size_t n_positions, float *host_out);
+
+/* Field volumes: SPHField.Interpolate (sph_field.go:124-135) at every point of a regular lattice (grid.Grid.GridPosition,
+ * geom/grid/point-grid.go:59-63), evaluated and left on the device.
+ *
+ * Voxel (i, j, k) lies at origin[a] + step[a] * (float)idx[a] per axis: float32, one multiplication and one addition, each
+ * rounded, never fused, in both math modes -- a caller reproduces every coordinate bit for bit.  The value is
+ * dsl_field_interpolate's at that point: the same sum, arithmetic and candidate order, the same scalar_buffer
+ * (DSL_BUF_DENSITIES or DSL_BUF_PRESSURES), the same treatment of boundary particles (a division by their density 0
+ * included) and of DSL_NEIGH_LSH_REF, on the current state (densities as left by the last dsl_density_pass).
+ *
+ * The output is dims[0] * dims[1] * dims[2] floats, x fastest: voxel (i, j, k) at (k * dims[1] + j) * dims[0] + i.  This is a
+ * deliberate departure from the reference's Grid.Index (point-grid.go:53-57), which is only right for cubes.
+ * dev_out is device memory: written asynchronously on the handle's stream, never read by the library.  host_out is a
+ * blocking copy.  Either may be NULL, not both; with host_out alone the library stages in an array of its own, allocated
+ * on first use, grown on demand, counted in DSL_OPT_DEVICE_BYTES and freed by dsl_destroy (DSL_ERR_NOMEM if it cannot be
+ * had: the handle stays usable).
+ *
+ * DSL_ERR_INVALID (dsl_last_error names the argument): a scalar_buffer other than the two, a dims entry < 1, more than
+ * 2^30 voxels, a step entry that is not finite and > 0, a non-finite origin, both outputs NULL.  DSL_ERR_UNSUPPORTED in
+ * slab mode, as for the field operators.  A refused call changes nothing.
+ *
+ * Like every entry point but the step drivers, the call first settles a live skin episode (DSL_OPT_SKIN): the next step
+ * sorts and rebuilds its lists.  Two kernel forms, DSL_OPT_VOLUME_BRICKS; every launch is timed under DSL_K_VOLUME. */
+int dsl_field_volume(dsl_handle *h, int scalar_buffer, const float origin[3], const float step[3],
+                     const int32_t dims[3], float *dev_out, float *host_out);
 
 /* Step drivers: one iteration of WCSPH.Run (solver/wcsph/wcsph.go:14-26) and of
  * PciMethod.Run (solver/pcisph/pcisph_darwin.go:43-101) per step.  Asynchronous: they
@@ -625,9 +651,20 @@ enum {
   DSL_OPT_COLLIDE_VISITS = 39,        /* (get, blocking) triangle records loaded, summed over the waves of the last collide pass or
                                          query that the indexed kernel ran (full-walk waves included); -1: the list walk ran it */
   DSL_OPT_COLLIDE_FULL_WAVES = 40,    /* (get, blocking) waves of that launch that walked the whole list (a slow lane); -1 likewise */
-  DSL_OPT_COLLIDE_SLAB = 41           /* (set/get, default 0) 1: a collider mesh on a slab handle -- dsl_collider_set_mesh and
+  DSL_OPT_COLLIDE_SLAB = 41,          /* (set/get, default 0) 1: a collider mesh on a slab handle -- dsl_collider_set_mesh and
                                          dsl_slab_config accept each other, in either order; the rules are at dsl_collide_pass.
                                          Back to 0 while a slab handle holds a mesh: DSL_ERR_INVALID, nothing changes */
+  /* dsl_field_volume.  1: DSL_MATH_FAST handles with grid neighbours sweep the lattice brick by brick (8 x 8 x 4 voxels
+   * per workgroup) out of an LDS image of the particles in reach of the brick; a brick whose image does not fit takes the
+   * per-voxel sweep over global memory.  0: the per-voxel sweep everywhere, bit for bit dsl_field_interpolate in both math
+   * modes (DSL_MATH_EXACT and DSL_NEIGH_LSH_REF always run it).  Both forms give the same bits.  Default 1: at step = h / 2
+   * the brick form is a quarter faster; at step >= h, where every brick inside the fluid falls back, it is a quarter slower
+   * and 0 is the better choice (DESIGN.md 4.3 has the measurement). */
+  DSL_OPT_VOLUME_BRICKS = 48,          /* (set/get, default 1) */
+  DSL_OPT_VOLUME_LDS_BRICKS = 49,      /* (get, blocking) bricks of the last call that swept out of LDS; 0: the per-voxel form ran */
+  DSL_OPT_VOLUME_FALLBACK_BRICKS = 50, /* (get, blocking) bricks of the last call whose image did not fit; 0 likewise */
+  DSL_OPT_VOLUME_EMPTY_BRICKS = 51,    /* (get, blocking) bricks of the last call with no particle in reach: zeros, nothing staged */
+  DSL_OPT_VOLUME_STAGED_RECORDS = 52   /* (get, blocking) particle records (20 bytes each) the LDS bricks of the last call staged */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
