@@ -1365,9 +1365,13 @@ static int field_div_curl(dsl_handle* h, int tensor_buffer, float* host_out, siz
   if (int rc = field_prepare(h, &n)) return rc;
   if (!host_out || count != (size_t)n_fluid_of(h) * (curl ? 3 : 1)) return fail(h, DSL_ERR_INVALID, "field operator: bad output size");
   CSoa3 t;
+  // (a read-out leaves the run alone: implicit forces are filled in for the kernel to read and stay implicit -- the step
+  // driver takes a plain step instead of a skin step whenever the forces are not)
+  const bool uniform = h->forces_uniform;
   if (tensor_buffer == DSL_BUF_VELOCITIES) t = cvel(h);
   else if (tensor_buffer == DSL_BUF_FORCES) {
     if (int rc = materialise_forces(h)) return rc;
+    h->forces_uniform = uniform;
     t = cfrc(h);
   } else return fail(h, DSL_ERR_INVALID, "field operator: tensor field must be velocities or forces");
   CSoa3 p = cpos(h);

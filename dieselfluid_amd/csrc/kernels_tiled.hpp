@@ -891,6 +891,16 @@ __device__ __forceinline__ float4 tile_record(const float* o, bool real, float o
   }
   return v;
 }
+// The expanded form of r^2 loses eps (|xi|^2 + |xj|^2 + 2 |xi.xj|) / h^2 of q to cancellation: ~2e-6 while target and
+// candidates lie within 3 cells of the tile centre, which holds for every particle inside the grid box.  A particle
+// that has left the box is clamped into an edge cell (cell_coord) and may be any distance from its tile's centre; its
+// neighbours out there are as far, and the error grows with the square of that distance (1.8e-4 of the density at 23
+// cells).  Such a TARGET keeps its sweep -- the force walk reads the mask words -- but takes its density from
+// density_global_fast, which forms r^2 from coordinate differences.  The density kernels carry the mark in the
+// target's self term (NaN), so the candidate loop holds no register for it.
+__device__ __forceinline__ bool tile_target_far(const DevConsts& c, const float4& me) {
+  return fmaxf(fmaxf(fabsf(me.x), fabsf(me.y)), fabsf(me.z)) > 3.0f * c.cell;  // (false for a NaN position)
+}
 // stage_commit's `store` for an image that holds nothing else
 struct StoreTileRecord {
   float4* img;
@@ -1165,7 +1175,8 @@ struct MaskQueue {
 // accumulation; the kernel is bound by FP32 issue, profiles/r01_v3_pmc.md).
 // Tile-relative values stay below 3.5 cells, which bounds the cancellation error of the
 // expanded form at ~2e-6 -- inside the FAST-mode tolerance, and invisible to the cut-off
-// (a candidate that far out contributes ~1e-12).
+// (a candidate that far out contributes ~1e-12).  A particle that has left the grid box is not bound by that:
+// tile_target_far.
 // ---------------------------------------------------------------------------------
 // EXACT = true (DSL_MATH_EXACT): the reference's own float32 operations, one rounding each
 // (sph_field.go:155-172, std_kernel.go:33-39, vector.go:301-308), summed in the reference's order --
@@ -1397,6 +1408,7 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
         // a particle whose position has gone NaN (the reference produces such next to boundary particles)
         // meets nobody, itself included: q is NaN, clamped to 0, for every candidate
         self_term = (me.x == me.x && me.y == me.y && me.z == me.z) ? 1.0f : 0.0f;
+        if (tile_target_far(c, me)) self_term = __uint_as_float(0x7fc00000u);  // (density from global memory, below)
         const float two_hh = 2.0f * c.inv_hh;
         const float sx = two_hh * me.x, sy = two_hh * me.y, sz = two_hh * me.z, a0 = 1.0f + me.w;
         // one x-run of candidates (row rr of the staged tile, the 3 cells around the target's)
@@ -1449,7 +1461,10 @@ __global__ __launch_bounds__(kTBlock, 4) void k_density_tiled(DevConsts c, TileG
         }
         if (sub != 0) return;
       }
-      if (!ovf) acc = (acc - self_term) * (c.mass * c.A);  // the particle met itself once (q = 1)
+      if (!ovf) {
+        if (self_term != self_term) acc = density_global_fast(c, cell_start, p, g);  // far from the tile centre: tile_target_far
+        else acc = (acc - self_term) * (c.mass * c.A);                            // the particle met itself once (q = 1)
+      }
       store_density_fast(c, bnd, rho, pterm, g, acc);
     });
     DSL_STAMP(d3);
@@ -1584,6 +1599,10 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
       // meets nobody, itself included: q is NaN, clamped to 0, for every candidate
       self_term[0] = (me0.x == me0.x && me0.y == me0.y && me0.z == me0.z) ? 1.0f : 0.0f;
       self_term[1] = (me1.x == me1.x && me1.y == me1.y && me1.z == me1.z) ? 1.0f : 0.0f;
+      if constexpr (!WIDE) {  // (density from global memory, below)
+        if (tile_target_far(c, me0)) self_term[0] = __uint_as_float(0x7fc00000u);
+        if (tile_target_far(c, me1)) self_term[1] = __uint_as_float(0x7fc00000u);
+      }
       const float two_hh = 2.0f * c.inv_hh;
       const float sx0 = two_hh * me0.x, sy0 = two_hh * me0.y, sz0 = two_hh * me0.z, a00 = 1.0f + me0.w;
       const float sx1 = two_hh * me1.x, sy1 = two_hh * me1.y, sz1 = two_hh * me1.z;
@@ -1658,7 +1677,8 @@ __global__ __launch_bounds__(kPBlock, 4) void k_density_pair(DevConsts c, TileGr
       for (int e = 0; e < 2; ++e) {
         if (e == 1 && !two) break;
         const int g = g0 + e;
-        const float a = (acc[e] - self_term[e]) * (c.mass * c.A);  // the particle met itself once (q = 1)
+        float a = (acc[e] - self_term[e]) * (c.mass * c.A);  // the particle met itself once (q = 1)
+        if (self_term[e] != self_term[e]) a = density_global_fast(c, cell_start, p, g);  // far from the tile centre: tile_target_far
         store_density_fast(c, bnd, rho, pterm, g, a);
       }
     });

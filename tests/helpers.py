@@ -113,6 +113,61 @@ def brute_force_step_f64(p, x, v, probe, near, force=None):
     return rho_p, x_new, v_new
 
 
+def field_ops_f64(p, x, v_or_f, rho, probe, queries=None):
+    """Div, Curl, Laplacian and Interpolate (sph_field.go:124-135,203-294) in float64, by brute force over all
+    particles, for the particles `probe` (index array) of the state (x, v_or_f, rho) and at the points `queries`.
+    `v_or_f` is the tensor field (velocities or forces, one row per particle), `rho` the float32 densities the
+    operators read (they are an input here, not recomputed); the pressure field is the Tait EOS of those densities
+    (field_types.go:39-42, model.go:92-101) with the scene's own eos_d0_grad, eos_w and eos_gamma and p0 = 0.  The
+    kernel is std_kernel.go:33-76: F = A (1 - r^2/h^2)^2, Grad = dir * (-B (1 - r/h)^2), O2D = C (1 - r/h), all for
+    r < h, with dir = (x_j - x_i) / r and dir = 0 at r = 0 (vector.go:322-331).  No boundary particles.
+
+      Div_i  = sum_j (m / rho_j) t_j . Grad_ij          Curl_i = sum_j (m / rho_j) t_j x Grad_ij          (j != i)
+      Lap_i  = sum_j m (f_j - f_i) / rho_j O2D(r_ij)                                                      (j != i)
+      Int(q) = sum_j (m / rho_j) F(|q - x_j|) f_j                                                         (every j)
+
+    Returns a dict: "div" (len(probe)), "curl" (len(probe), 3), "lap_density", "lap_pressure" (len(probe)) and, with
+    `queries`, "interp_density", "interp_pressure" (len(queries)).  Independent of the oracle and of the engine:
+    numpy only."""
+    h, m = float(p.h), float(p.mass)
+    PI = 3.141592653589
+    A, B, Ck = 315.0 / (64.0 * PI * h ** 3), -45.0 / (PI * h ** 4), 90.0 / (PI * h ** 5)
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(v_or_f, dtype=np.float64).reshape(-1, 3)
+    rho = np.asarray(rho, dtype=np.float64).reshape(-1)
+    probe = np.asarray(probe, dtype=np.int64).reshape(-1)
+    d0, w, g = float(p.eos_d0_grad), float(p.eos_w), float(p.eos_gamma)
+    press = (w / g) * ((np.maximum(rho, d0) / d0) ** g - 1.0)
+    vol = m / rho
+    out = {"div": np.zeros(probe.size), "curl": np.zeros((probe.size, 3)), "lap_density": np.zeros(probe.size),
+           "lap_pressure": np.zeros(probe.size)}
+    for k, i in enumerate(probe):
+        d = x - x[i]
+        r = np.sqrt((d * d).sum(axis=1))
+        msk = r < h
+        msk[i] = False
+        d, r, j = d[msk], r[msk], np.nonzero(msk)[0]
+        dirn = np.where(r[:, None] > 0, d / np.where(r > 0, r, 1.0)[:, None], 0.0)
+        grad = dirn * (-(B * (1.0 - r / h) ** 2))[:, None]
+        s = t[j] * vol[j][:, None]
+        out["div"][k] = (s * grad).sum()
+        out["curl"][k] = np.cross(s, grad).sum(axis=0)
+        o2 = Ck * (1.0 - r / h)
+        out["lap_density"][k] = (m * (rho[j] - rho[i]) / rho[j] * o2).sum()
+        out["lap_pressure"][k] = (m * (press[j] - press[i]) / rho[j] * o2).sum()
+    if queries is not None:
+        q = np.asarray(queries, dtype=np.float64).reshape(-1, 3)
+        out["interp_density"], out["interp_pressure"] = np.zeros(q.shape[0]), np.zeros(q.shape[0])
+        for k in range(q.shape[0]):
+            d = x - q[k]
+            r2 = (d * d).sum(axis=1)
+            j = np.nonzero(r2 < h * h)[0]
+            wgt = vol[j] * A * (1.0 - r2[j] / (h * h)) ** 2
+            out["interp_density"][k] = (wgt * rho[j]).sum()
+            out["interp_pressure"][k] = (wgt * press[j]).sum()
+    return out
+
+
 def fast_velocity_tolerance(p, steps, eps_rho=2.0e-6):
     """Absolute velocity tolerance (m/s) of DSL_MATH_FAST against the oracle after `steps` steps of a
     scene with the pressure force on.  Error model: FAST densities agree with the oracle to eps_rho ~ 2e-6
