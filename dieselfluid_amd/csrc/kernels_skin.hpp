@@ -44,6 +44,18 @@ constexpr unsigned int kLGlobal = 0xffffu;  // count sentinel: this particle tak
 constexpr float kSkinTauSteps = 16.0f;      // cap on SkinState::tau, in steps
 constexpr int kLQuads = 14;                 // staging: quads of 4 records per row and pass (36 rows x 14 = 504 lanes)
 static_assert(kTRows * kLQuads <= kLBlock, "one quad per lane");
+// DSL_LIST_WALK (build macro, A/B; a mask as DSL_STAGE_DEALT): bit 1 (the default, 2) k_force_list -- the full pass's walk
+// as straight-line code over the chunks ("Walking a list" below); 0 = the loop.  Bit 0 is the density walk's, which was
+// built the same way, gained nothing and keeps its loop (profiles/HISTORY.md, "List walks: straight-line code over the
+// chunks"): no code stands behind it.
+#ifndef DSL_LIST_WALK
+#define DSL_LIST_WALK 2
+#endif
+constexpr int kListWalk = DSL_LIST_WALK;
+// waves per SIMD the compiler is to hold k_force_list to (__launch_bounds__' second argument).  The loop stays below its
+// register cliff by itself; the straight-line walk does only when told: without a viscous term (one 40 KB image: the LDS
+// leaves room for three workgroups per CU) the kernel runs six waves per SIMD at <= 80 VGPRs.
+constexpr int force_list_waves(bool want_v) { return (kListWalk & 2) != 0 && !want_v ? 6 : 4; }
 
 // first kernel of every skin step: this step's rebuild flag.  The lists are good for the positions the previous step
 // left if no particle is further than s h / 2 from the reference position its list was built at; k_force_list measures
@@ -482,13 +494,65 @@ __device__ __forceinline__ unsigned int take_count(Chunk& e, unsigned int pad) {
   e.x = (e.x & 0xffff0000u) | pad;
   return cnt;
 }
+// Loads that only ONE successor of a branch uses are moved into that successor by the compiler: the records an exit of
+// the walk leaves unread would be requested behind the exit's branch, straight in front of their first use with no
+// arithmetic to hide behind, and a list chunk one and a half chunks late.  Loads do not cross this point (no instruction:
+// the compiler must assume that memory changes here); arithmetic does.  The lists are a `const __restrict__` argument,
+// which nothing can change: a walk reaches them through a pointer that has been through unknown_pointer().
+__device__ __forceinline__ void loads_issued() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+typedef unsigned int ListWords __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) ListWords* ListPtr;  // (global memory by type: nothing left to infer)
+__device__ __forceinline__ unsigned long long unknown_pointer(const uint4* p) {
+  unsigned long long a = reinterpret_cast<unsigned long long>(p);
+  asm volatile("" : "+v"(a));
+  return a;
+}
+__device__ __forceinline__ unsigned long long unknown_pointer_uniform(const uint4* p) {
+  unsigned long long a = reinterpret_cast<unsigned long long>(p);
+  asm volatile("" : "+s"(a));
+  return a;
+}
+// The chunks of one slot's list for a walk written as straight-line code (a full pass: the wave's lists have `nch`
+// chunks each, a scalar).  Chunk ch lives in c[ch % 3]; request(ch), at the head of chunk ch, loads chunk ch + 2 into the
+// place chunk ch - 1 has left.  The load is UNCONDITIONAL, so that the compiler counts the loads in flight (s_waitcnt
+// vmcnt(1)) where a branch around the load made it wait for all of them.  Past the list's end every lane asks for the
+// same 16 bytes, the last chunk of the wave's first list: one 64-byte line that the wave has asked for before, with
+// entries of this tile in it (a walk requests -- and never reads -- the records of a word or two behind its list's end).
+// `ch` is a constant of the unrolled walk: every chunk has registers of its own and nothing is copied from one place
+// to another.
+struct ChunkRing {
+  Chunk c[3];
+  unsigned long long next;  // address of this slot's chunk ch + 2
+  unsigned long long last;  // address of the last chunk of the wave's first list (a scalar)
+  int lstride, nch;
+  __device__ __forceinline__ ChunkRing(const uint4* __restrict__ lists, int lstride_, int g, int nch_, const Chunk& q0,
+                                       const Chunk& q1)
+      : next(unknown_pointer(lists + (size_t)2 * lstride_ + g)),
+        last(unknown_pointer_uniform(lists + (size_t)max(nch_ - 1, 0) * lstride_ + __builtin_amdgcn_readfirstlane(g))),
+        lstride(lstride_), nch(nch_) {
+    c[0] = q0;
+    c[1] = q1;
+  }
+  __device__ __forceinline__ void request(int ch) {
+    if (ch + 2 >= kLMaxChunks) return;
+    const ListWords v = *(ListPtr)(ch + 2 < nch ? next : last);
+    c[(ch + 2) % 3] = Chunk{v.x, v.y, v.z, v.w};
+    next += (unsigned long long)lstride * sizeof(uint4);
+  }
+  __device__ __forceinline__ const Chunk& at(int ch) const { return c[ch % 3]; }
+};
 __device__ __forceinline__ int chunks_of(unsigned int cnt) { return cnt == kLGlobal ? 0 : (int)((cnt + kLEntries) >> 3); }
 
 // ---------------------------------------------------------------------------------
-// Walking a list.  Full pass (one lane per target): the wave's lists all have the length field 0 names, so the loop over
+// Walking a list.  Full pass (one lane per target): the wave's lists all have the length field 0 names, so the walk over
 // its fields is scalar; `fetch(word)` requests the records of a 32-bit word's two fields, the walk bodies below
-// pipeline them.  Short pass (k lanes per target, lane `sub` takes chunks sub, sub + k, ...): plain and unpipelined --
-// the handful of targets beyond a block, or a sparse tile.
+// pipeline them -- as a loop over the chunks, or (DSL_LIST_WALK) as straight-line code over all kLMaxChunks of them with
+// the loop's exits, in which every chunk has registers of its own (ChunkRing) and loads stay where the source issues
+// them (loads_issued).  Short pass (k lanes per target, lane `sub` takes chunks sub, sub + k, ...): plain and
+// unpipelined -- the handful of targets beyond a block, or a sparse tile.
 // ---------------------------------------------------------------------------------
 // shared pass: calls body(chunk) for every chunk of this lane's share; lanes whose share has ended get the far-away chunk
 // until the wave's longest share is through (`fields` = field 0 of the target's first chunk, from the group's lane 0)
@@ -606,7 +670,9 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
         } else {
           // The wave's lists have one length (k_list_build): a scalar loop over its fields, software-pipelined in groups
           // of four -- the next group's records are requested before the current group's arithmetic, across chunk
-          // boundaries too, so that the LDS pipe and the VALU work at the same time.
+          // boundaries too, so that the LDS pipe and the VALU work at the same time.  (As compiled, chunk ch + 2 is
+          // waited for in the trip that requests it.  Straight-line code as in k_force_list keeps two chunks in flight
+          // and is no faster, 0.404 -> 0.407 ms: profiles/HISTORY.md, "List walks: straight-line code over the chunks".)
           const int nf = __builtin_amdgcn_readfirstlane((int)fields), nch = (nf + kLEntries - 1) >> 3;
           const uint4* lp = lists + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
           Chunk e = q0, e1 = q1;
@@ -661,7 +727,7 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
 // Also tracks the step's max |v|^2 for the skin's displacement bound.
 // ---------------------------------------------------------------------------------
 template <bool WANT_G, bool WANT_V, bool QUEUE>
-__global__ __launch_bounds__(kLBlock, 4) void k_force_list(DevConsts c, TileGrid tg, const int* __restrict__ desc_of,
+__global__ __launch_bounds__(kLBlock, force_list_waves(WANT_V)) void k_force_list(DevConsts c, TileGrid tg, const int* __restrict__ desc_of,
                                                            const int* __restrict__ n_tiles, const int* __restrict__ desc,
                                                            const int* __restrict__ cell_start, SkinState* st, CSoa3 pX,
                                                            CSoa3 vX, CSoa3 pZ, CSoa3 vZ, CSoa3 pR, const float* __restrict__ rho,
@@ -807,35 +873,65 @@ __global__ __launch_bounds__(kLBlock, 4) void k_force_list(DevConsts c, TileGrid
               }
             });
           } else {
-            // the wave's lists have one length (k_list_build): a scalar loop over the 32-bit words of the chunks;
-            // p0, p1 hold the records of the word being walked, every step consumes one and requests the field two
-            // ahead, so four reads are in flight while a pair's ~25 VALU instructions issue
+            // The wave's lists have one length (k_list_build): a scalar walk over the 32-bit words of the chunks.  p0, p1
+            // hold the records of the word being walked, every step consumes one and requests the field two ahead, so
+            // four reads are in flight while a pair's ~25 VALU instructions issue.
+            constexpr bool kStraight = (kListWalk & 2) != 0;
             const int nf = __builtin_amdgcn_readfirstlane((int)fields), nch = (nf + kLEntries - 1) >> 3;
-            const uint4* lp = lists + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
-            Chunk e = q0, e1 = q1;
-            Pair1 p0 = fetch1(e.x & 0xffffu), p1 = fetch1(e.x >> 16);
+            Pair1 p0 = fetch1(q0.x & 0xffffu), p1 = fetch1(q0.x >> 16);
             auto word = [&](unsigned int next_word) {
               Pair1 cu = p0;
               p0 = fetch1(next_word & 0xffffu);
+              if constexpr (kStraight) loads_issued();
               accum(cu.a, cu.b);
               cu = p1;
               p1 = fetch1(next_word >> 16);
+              if constexpr (kStraight) loads_issued();
               accum(cu.a, cu.b);
             };
-            for (int ch = 0;;) {
-              word(e.y);
-              if (8 * ch + 2 >= nf) break;  // (the word just requested is never read: four reads more)
-              word(e.z);
-              if (8 * ch + 4 >= nf) break;
-              word(e.w);
-              if (8 * ch + 6 >= nf) break;
-              const Chunk en = e1;
-              if (ch + 2 < nch) e1 = load_chunk(lp, 0);
-              lp += lstride;
-              word(en.x);
-              e = en;
-              ch += 1;
-              if (8 * ch >= nf) break;
+            if constexpr (kStraight) {
+              // Straight-line code over the chunks (DSL_LIST_WALK bit 1): chunk ch + 2 is requested at the head of chunk
+              // ch and first read seven words later, with the request of chunk ch + 3 in between (s_waitcnt vmcnt(1)),
+              // and the two reads of a field stand two pairs' arithmetic in front of their use.  The loop below says the
+              // same and is not compiled so: the chunk is waited for in the trip that requests it (its registers are
+              // copied over the back edge), and the reads an exit leaves unread sink behind the exit's branch.
+              ChunkRing ring(lists, lstride, g, nch, q0, q1);
+#pragma unroll
+              for (int ch = 0; ch < kLMaxChunks; ++ch) {
+                ring.request(ch);
+                const Chunk& e = ring.at(ch);
+                word(e.y);
+                if (8 * ch + 2 >= nf) break;  // (the word just requested is never read: four reads more)
+                word(e.z);
+                if (8 * ch + 4 >= nf) break;
+                word(e.w);
+                if (8 * ch + 6 >= nf) break;
+                if (ch + 1 == kLMaxChunks) {  // (no chunk behind the last: its fourth word ends the walk)
+                  accum(p0.a, p0.b);
+                  accum(p1.a, p1.b);
+                  break;
+                }
+                word(ring.at(ch + 1).x);
+                if (8 * ch + 8 >= nf) break;
+              }
+            } else {
+              const uint4* lp = lists + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
+              Chunk e = q0, e1 = q1;
+              for (int ch = 0;;) {
+                word(e.y);
+                if (8 * ch + 2 >= nf) break;  // (the word just requested is never read: four reads more)
+                word(e.z);
+                if (8 * ch + 4 >= nf) break;
+                word(e.w);
+                if (8 * ch + 6 >= nf) break;
+                const Chunk en = e1;
+                if (ch + 2 < nch) e1 = load_chunk(lp, 0);
+                lp += lstride;
+                word(en.x);
+                e = en;
+                ch += 1;
+                if (8 * ch >= nf) break;
+              }
             }
           }
         }
