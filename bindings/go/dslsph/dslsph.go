@@ -174,6 +174,67 @@ func (e *Engine) InterpolateGrid(scalarBuffer C.int, origin, step [3]float32, di
 		(*C.int32_t)(unsafe.Pointer(&dims[0])), (*C.float)(devOut), host))
 }
 
+// SurfaceExtract: the iso-surface triangles of a device volume on InterpolateGrid's lattice (include/dslsph.h has the
+// rule).  devVertices (9 floats per triangle) and devNormals (3, may be nil) take the first min(T, capTriangles) triangles,
+// devCount (an int64 of device memory, may be nil) the full number T.  wantCount: T comes back too (a blocking 8-byte copy);
+// without it the call is asynchronous on the engine's stream and returns -1.
+func (e *Engine) SurfaceExtract(devVolume unsafe.Pointer, origin, step [3]float32, dims [3]int32, iso float32,
+	devVertices, devNormals unsafe.Pointer, capTriangles int, devCount unsafe.Pointer, wantCount bool) (int64, error) {
+	n := C.int64_t(-1)
+	var hostCount *C.int64_t
+	if wantCount {
+		hostCount = &n
+	}
+	err := e.ck(C.dsl_surface_extract(e.h, (*C.float)(devVolume), (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])),
+		(*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(iso), (*C.float)(devVertices), (*C.float)(devNormals),
+		C.size_t(capTriangles), (*C.int64_t)(devCount), hostCount))
+	return int64(n), err
+}
+
+// FieldSurface: InterpolateGrid and SurfaceExtract in one call, for a host without device memory: the first
+// min(T, len(vertices)/9, len(normals)/3) triangles into vertices and, unless nil, normals (3 floats per triangle); returns T.
+func (e *Engine) FieldSurface(scalarBuffer C.int, origin, step [3]float32, dims [3]int32, iso float32, vertices, normals []float32) (int64, error) {
+	var n C.int64_t
+	var vp, np *C.float
+	capTriangles := len(vertices) / 9
+	if len(vertices) > 0 {
+		vp = (*C.float)(unsafe.Pointer(&vertices[0]))
+	}
+	if len(normals) > 0 {
+		np = (*C.float)(unsafe.Pointer(&normals[0]))
+		if len(normals)/3 < capTriangles { // (both slices take the same triangles)
+			capTriangles = len(normals) / 3
+		}
+	}
+	err := e.ck(C.dsl_field_surface(e.h, scalarBuffer, (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])),
+		(*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(iso), vp, np, C.size_t(capTriangles), &n))
+	return int64(n), err
+}
+
+// Surface: the fluid's iso-surface in mesh.Mesh order (geom/mesh/mesh.go:11-14): Vertexes as 3 * T points of 3 floats,
+// Normals as T.  The buffer is sized from a guess (four triangles per voxel of the lattice's three faces) and FieldSurface is
+// called a second time only when the guess was short.
+func (e *Engine) Surface(scalarBuffer C.int, origin, step [3]float32, dims [3]int32, iso float32) (vertices, normals []float32, err error) {
+	nx, ny, nz := int(dims[0]), int(dims[1]), int(dims[2])
+	guess := 4 * (nx*ny + ny*nz + nz*nx)
+	if guess < 1024 {
+		guess = 1024
+	}
+	for try := 0; try < 2; try++ {
+		vertices = make([]float32, 9*guess)
+		normals = make([]float32, 3*guess)
+		t, err := e.FieldSurface(scalarBuffer, origin, step, dims, iso, vertices, normals)
+		if err != nil {
+			return nil, nil, err
+		}
+		if int(t) <= guess {
+			return vertices[:9*int(t)], normals[:3*int(t)], nil
+		}
+		guess = int(t)
+	}
+	return nil, nil, errors.New("dslsph: Surface: the triangle count changed between two calls")
+}
+
 // ---- render hand-off without the per-step full read-back (pcisph_gpu_darwin.go:276-282) ----
 
 // DownloadDecimated: every stride-th particle of positions / velocities.
@@ -535,6 +596,9 @@ const (
 	OptCollideFullWaves    = int(C.DSL_OPT_COLLIDE_FULL_WAVES)
 	// a collider mesh on a slab handle: every rank sets the same mesh, the slab step drivers collide after each integrate
 	OptCollideSlab = int(C.DSL_OPT_COLLIDE_SLAB)
+	// the last SurfaceExtract / FieldSurface: its triangles T, its bricks of 8 x 8 x 4 cubes with a triangle
+	OptSurfaceTriangles    = int(C.DSL_OPT_SURFACE_TRIANGLES)
+	OptSurfaceActiveBricks = int(C.DSL_OPT_SURFACE_ACTIVE_BRICKS)
 )
 
 // SetOption / GetOption: library options (DSL_OPT_* in include/dslsph.h), e.g. the neighbour-list skin of WCSPHStep.

@@ -776,6 +776,7 @@ void free_all(dsl_handle* h) {
   col_index_free(h);
   (void)hipFree(h->vol_stage);
   (void)hipFree(h->vol_ctr);
+  surface_free(h);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1789,6 +1790,11 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
     case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);
     case DSL_OPT_VOLUME_STAGED_RECORDS: return volume_brick_count(h, 3, value);
+    case DSL_OPT_SURFACE_TRIANGLES:
+    case DSL_OPT_SURFACE_ACTIVE_BRICKS:
+    case DSL_OPT_SURFACE_COUNT_MS:
+    case DSL_OPT_SURFACE_SCAN_MS:
+    case DSL_OPT_SURFACE_EMIT_MS: return surface_option(h, option, value);  // (blocking: the kernels count on the device)
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }

@@ -5,7 +5,8 @@
 //   dslsph.hip         the engine: every kernel launch of the kernel headers, the passes, the single-GPU step drivers
 //   collider_host.hip  the collider's host side (the kernels are in collide.hip, collide_index.hip, collide_slab.hip)
 //   slab_link.hip      multi-GPU: communicator, slab link, re-balancing, the native slab step drivers
-//   volume.hip         field volumes: dsl_field_volume and its two kernels (the one host unit with kernels of its own)
+//   volume.hip         field volumes: dsl_field_volume and its two kernels (a host unit with kernels of its own)
+//   surface.hip        fluid surfaces: dsl_surface_extract, dsl_field_surface and their four kernels (likewise)
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -177,6 +178,17 @@ struct dsl_handle {
   unsigned long long* vol_ctr = nullptr;
   bool vol_bricks = true;  // DSL_OPT_VOLUME_BRICKS (the measured choice: DESIGN.md 4.3)
   bool vol_last_bricks = false;
+  // fluid surfaces (surface.hip; dsl_surface_extract).  surf_scan: one 64-bit count, then offset, per brick of 8 x 8 x 4 cubes and
+  // the scan's upper levels behind them; surf_ctr: [0] triangles T, [1] bricks with a triangle, of the last call; surf_stage:
+  // dsl_field_surface's triangles before they go to the host.  All three allocated on first use and grown on demand.
+  // surf_ev: the last call's phase boundaries (count | scan | . emit |) while timing is on; surf_timed: 0 none, 1 count and scan, 2 all
+  unsigned long long* surf_scan = nullptr;
+  size_t surf_scan_count = 0;
+  unsigned long long* surf_ctr = nullptr;
+  float* surf_stage = nullptr;
+  size_t surf_stage_count = 0;
+  hipEvent_t surf_ev[5] = {};
+  int surf_timed = 0;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -294,5 +306,12 @@ int collide_pass(dsl_handle* h);
 
 // ---- defined in volume.hip ----
 int volume_brick_count(dsl_handle* h, int which, double* value);  // DSL_OPT_VOLUME_LDS_BRICKS (0), _FALLBACK_BRICKS, _EMPTY_BRICKS, _STAGED_RECORDS (3)
+
+// dsl_field_volume into vol_stage alone, with every refusal of dsl_field_volume (dsl_field_surface)
+int field_volume_staged(dsl_handle* h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3]);
+
+// ---- defined in surface.hip ----
+int surface_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SURFACE_* (get)
+void surface_free(dsl_handle* h);
 
 }  // namespace dsl

@@ -228,9 +228,10 @@ int volume_brick_count(dsl_handle* h, int which, double* value) {
 
 using namespace dsl;
 
-int dsl_field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3],
-                     float* dev_out, float* host_out) {
-  CHECK_HANDLE_ONLY(h);
+namespace {
+// dsl_field_volume; to_stage: into the library's staging array, which is then the only output (dsl_field_surface)
+int field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3],
+                 float* dev_out, float* host_out, bool to_stage) {
   // every refusal comes before anything is touched, the skin episode included
   if (h->c.n_ptr || h->c.slab_axis >= 0) return fail(h, DSL_ERR_UNSUPPORTED, "field operators are not available in slab mode");
   const int field = scalar_buffer == DSL_BUF_DENSITIES ? 0 : (scalar_buffer == DSL_BUF_PRESSURES ? 1 : -1);
@@ -248,7 +249,7 @@ int dsl_field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], co
     g.s[a] = step[a];
     g.n[a] = dims[a];
   }
-  if (!dev_out && !host_out) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: dev_out and host_out are both NULL");
+  if (!dev_out && !host_out && !to_stage) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: dev_out and host_out are both NULL");
   if (h->skin_live)
     if (int rc = skin_settle(h)) return rc;
   if (int rc = ensure_grid(h)) return rc;
@@ -299,4 +300,17 @@ int dsl_field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], co
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
   return DSL_OK;
+}
+}  // namespace
+
+namespace dsl {
+int field_volume_staged(dsl_handle* h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3]) {
+  return field_volume(h, scalar_buffer, origin, step, dims, nullptr, nullptr, true);
+}
+}  // namespace dsl
+
+int dsl_field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3],
+                     float* dev_out, float* host_out) {
+  CHECK_HANDLE_ONLY(h);
+  return field_volume(h, scalar_buffer, origin, step, dims, dev_out, host_out, false);
 }

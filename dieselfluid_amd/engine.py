@@ -21,7 +21,7 @@ _COMPS = {0: 3, 1: 3, 2: 3, 3: 1, 4: 1, 5: 3, 6: 3}
 KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
-    "neigh_lists": 13, "collide": 14, "volume": 15,
+    "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16,
 }
 
 
@@ -528,6 +528,47 @@ class SPHEngine:
         self._ck(self._L.dsl_field_volume(self._h, BUF[scalar], _fp(o), _fp(s), ip, None, _fp(out)))
         return out.reshape(int(d[2]), int(d[1]), int(d[0]))
 
+    @staticmethod
+    def _lattice(origin, step, dims):
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float32), (3,)))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(step, dtype=np.float32), (3,)))
+        d = np.ascontiguousarray(dims, dtype=np.int32).reshape(3)
+        return o, s, d
+
+    def surface_extract(self, dev_volume, origin, step, dims, iso, dev_vertices=None, dev_normals=None, cap: int = 0,
+                        dev_count=None, want_count: bool = True):
+        """The iso-surface triangles of a device volume on field_volume's lattice (include/dslsph.h: dsl_surface_extract).
+        Every dev_* argument is a device pointer (an int) or None: the first min(T, cap) triangles go to dev_vertices (9 floats
+        each) and dev_normals (3 each), the full number T to the int64 at dev_count.  Returns T (a blocking 8-byte copy), or
+        None with want_count = False: the call is then asynchronous on the engine's stream."""
+        o, s, d = self._lattice(origin, step, dims)
+        n = C.c_int64(-1)
+        self._ck(self._L.dsl_surface_extract(self._h, C.c_void_p(dev_volume), _fp(o), _fp(s), d.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             C.c_float(iso), C.c_void_p(dev_vertices), C.c_void_p(dev_normals), int(cap),
+                                             C.c_void_p(dev_count), C.byref(n) if want_count else None))
+        return int(n.value) if want_count else None
+
+    def field_surface(self, origin, step, dims, iso, scalar: str = "densities", guess: int = 0):
+        """field_volume and the iso-surface of it in one call: (T, 3, 3) vertices and (T, 3) normals, in mesh.Mesh order.  The
+        host buffer is sized from a guess -- `guess` triangles, or four per voxel of the lattice's three faces (a surface
+        grows with the lattice's area, not its volume) -- and the library is called again only when the guess was short."""
+        o, s, d = self._lattice(origin, step, dims)
+        ip = d.ctypes.data_as(C.POINTER(C.c_int32))
+        if guess <= 0:
+            nx, ny, nz = (max(int(v), 1) for v in d)
+            guess = max(1024, 4 * (nx * ny + ny * nz + nz * nx))
+        n = C.c_int64(0)
+        for _ in range(2):
+            cap = int(guess)
+            verts = np.empty((cap, 3, 3), dtype=np.float32)
+            norms = np.empty((cap, 3), dtype=np.float32)
+            self._ck(self._L.dsl_field_surface(self._h, BUF[scalar], _fp(o), _fp(s), ip, C.c_float(iso), _fp(verts), _fp(norms), cap,
+                                               C.byref(n)))
+            if n.value <= cap:
+                break
+            guess = n.value
+        return verts[:n.value].copy(), norms[:n.value].copy()
+
     # -- solver drivers -----------------------------------------------------------
     def wcsph_step(self, nsteps: int = 1):
         self._ck(self._L.dsl_wcsph_step(self._h, int(nsteps)))
@@ -562,7 +603,9 @@ class SPHEngine:
                "collide_index": 35, "collide_index_edge": 36, "collide_index_cells": 37, "collide_index_entries": 38,
                "collide_visits": 39, "collide_full_waves": 40, "collide_slab": 41,
                "volume_bricks": 48, "volume_lds_bricks": 49, "volume_fallback_bricks": 50,
-               "volume_empty_bricks": 51, "volume_staged_records": 52}
+               "volume_empty_bricks": 51, "volume_staged_records": 52,
+               "surface_triangles": 56, "surface_active_bricks": 57, "surface_count_ms": 58, "surface_scan_ms": 59,
+               "surface_emit_ms": 60}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

@@ -317,6 +317,31 @@ class SPH {
     ck(dsl_collider_set_mesh(h_, verts.data(), normals.data(), normals.size() / 3, r, e));
   }
 
+  // The fluid's surface as a mesh.Mesh (README.MD:38 "SPH/Fluid Surfaces"; the reference's renderer draws meshes): the
+  // iso-surface of SPHField.Interpolate on the lattice origin + step * (i, j, k), evaluated, triangulated and wound on the
+  // device (include/dslsph.h: dsl_field_surface).  density = false: the pressure field.  The buffer is sized from a guess --
+  // four triangles per voxel of the lattice's three faces -- and the library is called again only when that was short.
+  mesh::Mesh Surface(const float origin[3], const float step[3], const int32_t dims[3], float iso, bool density = true) {
+    size_t cap = 4 * ((size_t)dims[0] * dims[1] + (size_t)dims[1] * dims[2] + (size_t)dims[2] * dims[0]);
+    if (cap < 1024) cap = 1024;
+    std::vector<float> verts, normals;
+    int64_t T = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      verts.resize(9 * cap);
+      normals.resize(3 * cap);
+      ck(dsl_field_surface(h_, density ? DSL_BUF_DENSITIES : DSL_BUF_PRESSURES, origin, step, dims, iso, verts.data(), normals.data(),
+                           cap, &T));
+      if ((size_t)T <= cap) break;
+      cap = (size_t)T;
+    }
+    mesh::Mesh m;
+    m.Vertexes.resize(3 * (size_t)T);
+    m.Normals.resize((size_t)T);
+    for (size_t v = 0; v < 3 * (size_t)T; ++v) m.Vertexes[v] = {verts[3 * v], verts[3 * v + 1], verts[3 * v + 2]};
+    for (size_t t = 0; t < (size_t)T; ++t) m.Normals[t] = {normals[3 * t], normals[3 * t + 1], normals[3 * t + 2]};
+    return m;
+  }
+
   int N() const { return particles_; }                 // fluid.go:106-108
   void NN() { ck(dsl_build_neighbours(h_)); }          // fluid.go:100-102
   float CFL() {                                        // fluid.go:111-114

@@ -152,7 +152,8 @@ enum {
   DSL_K_NEIGH_LISTS = 13, /* skin step: wide candidate sweep + neighbour lists (rebuild steps only) */
   DSL_K_COLLIDE = 14,     /* triangle-mesh collider: query + response (only while a mesh is set) */
   DSL_K_VOLUME = 15,      /* dsl_field_volume: the lattice sweep, either form */
-  DSL_K_COUNT = 16
+  DSL_K_SURFACE = 16,     /* dsl_surface_extract: its count, scan and emit launches, one entry each */
+  DSL_K_COUNT = 17
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -262,6 +263,55 @@ int dsl_field_interpolate(dsl_handle *h, int scalar_buffer, const float *host_po
  * sorts and rebuilds its lists.  Two kernel forms, DSL_OPT_VOLUME_BRICKS; every launch is timed under DSL_K_VOLUME. */
 int dsl_field_volume(dsl_handle *h, int scalar_buffer, const float origin[3], const float step[3],
                      const int32_t dims[3], float *dev_out, float *host_out);
+
+/* Fluid surfaces: the iso-surface of a volume on dsl_field_volume's lattice, as triangles in the reference's mesh.Mesh
+ * layout (geom/mesh/mesh.go:11-14; dsl_collider_set_mesh takes the same): 9 floats of vertices per triangle, 3 of normal.
+ *
+ * The rule is build-defined (the reference has no extractor): marching tetrahedra.  A cube is the 8 voxels (i..i+1, j..j+1,
+ * k..k+1), corner c at offset (c & 1, (c >> 1) & 1, (c >> 2) & 1); cubes are numbered x fastest.  Every cube splits into the
+ * same six tetrahedra around the diagonal from corner 0 to corner 7: for the axis permutations (a, b, c) in the order xyz, xzy,
+ * yxz, yzx, zxy, zyx the tetrahedron {0, e_a, e_a | e_b, 7}.  A voxel is inside when value >= iso.  A tetrahedron with one
+ * vertex i alone on its side gives one triangle through the edge points P(i, j) of the other three vertices j, ascending;
+ * two inside a < b and two outside c < d give the quad P(a, c), P(a, d), P(b, d), P(b, c) as (q0, q1, q2) and (q0, q2, q3).
+ * Winding comes from a table (csrc/surface_table.hpp, generated by tools/make_surface_table.py): a triangle whose normal
+ * would point inwards has its second and third vertex exchanged, so (b - a) x (c - a) points from inside to outside, towards
+ * lower values.  An edge point lies on the edge from the voxel with the smaller linear index u to the larger w:
+ * t = (iso - v_u) / (v_w - v_u), p = x_u + t * (x_w - x_u) per component with x = origin + step * idx as in dsl_field_volume:
+ * float32, every operation rounded once, IEEE division, nothing fused, the same in both math modes -- every cube that
+ * shares an edge computes the same bits, so the triangles join exactly.  The normal is n = (b - a) x (c - a) (differences
+ * and products each rounded) divided by len = sqrt((nx^2 + ny^2) + nz^2), or (0, 0, 0) when len is not > 0.
+ * A cube with a corner that is not finite emits nothing: boundary particles make NaN voxels (dsl_add_boundary_particles),
+ * and the surface has a HOLE there.  A voxel that equals iso exactly makes triangles of zero area; they are kept, so the
+ * count depends on the inside masks alone.  At most 12 triangles per cube.
+ * Order: bricks of 8 x 8 x 4 cubes ascending (x fastest; the first brick starts at cube 0), inside a brick its cubes
+ * ascending (x fastest), tetrahedra 0..5 inside a cube, table order inside a tetrahedron.  Every position comes from counts
+ * and a prefix sum, none from an atomic: two runs give the same bytes.
+ *
+ * dsl_surface_extract reads dev_volume (dims[0] * dims[1] * dims[2] floats of device memory, x fastest) and no particle
+ * state: it does not settle a live skin episode and works on slab handles too.  It writes the first min(T, cap_triangles)
+ * triangles to dev_vertices (9 floats each) and, unless NULL, dev_normals (3 floats each), and nothing beyond them; T, the
+ * full number of triangles whatever the capacity, goes to dev_count (device memory, unless NULL) and to host_count.
+ * Asynchronous on the handle's stream unless host_count is given: that is a blocking 8-byte copy.  cap_triangles = 0 with
+ * NULL outputs is the counting call.  A dims entry of 1 means no cubes: T = 0.  The library keeps 8 bytes per brick of
+ * 8 x 8 x 4 cubes (and 1/255 more) of its own, grown on demand and counted in DSL_OPT_DEVICE_BYTES.  Offsets are 64-bit;
+ * the voxel limit is dsl_field_volume's 2^30.
+ * DSL_ERR_INVALID (dsl_last_error names the argument): dev_volume NULL, a dims entry < 1, more than 2^30 voxels, a step
+ * entry that is not finite and > 0, a non-finite origin or iso, cap_triangles > 0 with dev_vertices NULL.  A refused call
+ * touches nothing.
+ *
+ * dsl_field_surface is the end-to-end call for a host without device memory: dsl_field_volume into the library's staging
+ * array, the extraction into a second array of the library's own (grown on demand, counted in DSL_OPT_DEVICE_BYTES, freed by
+ * dsl_destroy), and a blocking copy of the first min(T, cap_triangles) triangles; *n_triangles = T.  Refusals and slab
+ * behaviour (DSL_ERR_UNSUPPORTED) are dsl_field_volume's, plus a non-finite iso and cap_triangles > 0 with host_vertices
+ * NULL; like dsl_field_volume it settles a live skin episode.
+ *
+ * Launches are timed under DSL_K_SURFACE.  DSL_OPT_SURFACE_TRIANGLES and DSL_OPT_SURFACE_ACTIVE_BRICKS describe the last call. */
+int dsl_surface_extract(dsl_handle *h, const float *dev_volume, const float origin[3], const float step[3],
+                        const int32_t dims[3], float iso, float *dev_vertices, float *dev_normals,
+                        size_t cap_triangles, int64_t *dev_count, int64_t *host_count);
+int dsl_field_surface(dsl_handle *h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3],
+                      float iso, float *host_vertices, float *host_normals, size_t cap_triangles,
+                      int64_t *n_triangles);
 
 /* Step drivers: one iteration of WCSPH.Run (solver/wcsph/wcsph.go:14-26) and of
  * PciMethod.Run (solver/pcisph/pcisph_darwin.go:43-101) per step.  Asynchronous: they
@@ -664,7 +714,13 @@ enum {
   DSL_OPT_VOLUME_LDS_BRICKS = 49,      /* (get, blocking) bricks of the last call that swept out of LDS; 0: the per-voxel form ran */
   DSL_OPT_VOLUME_FALLBACK_BRICKS = 50, /* (get, blocking) bricks of the last call whose image did not fit; 0 likewise */
   DSL_OPT_VOLUME_EMPTY_BRICKS = 51,    /* (get, blocking) bricks of the last call with no particle in reach: zeros, nothing staged */
-  DSL_OPT_VOLUME_STAGED_RECORDS = 52   /* (get, blocking) particle records (20 bytes each) the LDS bricks of the last call staged */
+  DSL_OPT_VOLUME_STAGED_RECORDS = 52,  /* (get, blocking) particle records (20 bytes each) the LDS bricks of the last call staged */
+  /* dsl_surface_extract / dsl_field_surface, the last call's */
+  DSL_OPT_SURFACE_TRIANGLES = 56,      /* (get, blocking) T, the full number of triangles */
+  DSL_OPT_SURFACE_ACTIVE_BRICKS = 57,  /* (get, blocking) bricks of 8 x 8 x 4 cubes that emitted at least one triangle */
+  DSL_OPT_SURFACE_COUNT_MS = 58,       /* (get, blocking) milliseconds of its count launch, from device events recorded while */
+  DSL_OPT_SURFACE_SCAN_MS = 59,        /* dsl_timing_enable(1) holds (0 otherwise); its scan launches; */
+  DSL_OPT_SURFACE_EMIT_MS = 60         /* its emit launch (0 for a call that emitted nothing) */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
