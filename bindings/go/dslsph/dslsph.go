@@ -235,6 +235,86 @@ func (e *Engine) Surface(scalarBuffer C.int, origin, step [3]float32, dims [3]in
 	return nil, nil, errors.New("dslsph: Surface: the triangle count changed between two calls")
 }
 
+// SurfaceExtractIndexed: the same surface as an indexed mesh (include/dslsph.h: dsl_surface_extract_indexed).  devPositions
+// and devNormals (3 floats per vertex; devNormals may be nil) take the first min(V, capVertices) vertices, devIndices (3 int32
+// per triangle) the first min(T, capTriangles) triples, devCounts (two int64 of device memory, may be nil) V and T.
+// wantCounts: V and T come back too (a blocking copy); without it the call is asynchronous and returns -1, -1.  The mesh is
+// complete only when both capacities suffice.
+func (e *Engine) SurfaceExtractIndexed(devVolume unsafe.Pointer, origin, step [3]float32, dims [3]int32, iso float32,
+	devPositions, devNormals unsafe.Pointer, capVertices int, devIndices unsafe.Pointer, capTriangles int,
+	devCounts unsafe.Pointer, wantCounts bool) (int64, int64, error) {
+	n := [2]C.int64_t{-1, -1}
+	var hostCounts *C.int64_t
+	if wantCounts {
+		hostCounts = &n[0]
+	}
+	err := e.ck(C.dsl_surface_extract_indexed(e.h, (*C.float)(devVolume), (*C.float)(unsafe.Pointer(&origin[0])),
+		(*C.float)(unsafe.Pointer(&step[0])), (*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(iso), (*C.float)(devPositions),
+		(*C.float)(devNormals), C.size_t(capVertices), (*C.int32_t)(devIndices), C.size_t(capTriangles), (*C.int64_t)(devCounts),
+		hostCounts))
+	return int64(n[0]), int64(n[1]), err
+}
+
+// FieldSurfaceIndexed: InterpolateGrid and SurfaceExtractIndexed in one call, for a host without device memory: the first
+// min(V, len(positions)/3, len(normals)/3) vertices into positions and, unless nil, normals; the first min(T, len(indices)/3)
+// triples into indices; returns V and T.
+func (e *Engine) FieldSurfaceIndexed(scalarBuffer C.int, origin, step [3]float32, dims [3]int32, iso float32,
+	positions, normals []float32, indices []int32) (int64, int64, error) {
+	var n [2]C.int64_t
+	var pp, np *C.float
+	var ip *C.int32_t
+	capVertices, capTriangles := len(positions)/3, len(indices)/3
+	if len(positions) > 0 {
+		pp = (*C.float)(unsafe.Pointer(&positions[0]))
+	}
+	if len(normals) > 0 {
+		np = (*C.float)(unsafe.Pointer(&normals[0]))
+		if len(normals)/3 < capVertices { // (both slices take the same vertices)
+			capVertices = len(normals) / 3
+		}
+	}
+	if len(indices) > 0 {
+		ip = (*C.int32_t)(unsafe.Pointer(&indices[0]))
+	}
+	err := e.ck(C.dsl_field_surface_indexed(e.h, scalarBuffer, (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])),
+		(*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(iso), pp, np, C.size_t(capVertices), ip, C.size_t(capTriangles), &n[0]))
+	return int64(n[0]), int64(n[1]), err
+}
+
+// SurfaceIndexed: the fluid's iso-surface as positions, vertex normals (3 floats per vertex) and indices (3 per triangle).
+// The buffers are sized from a guess (two vertices and four triangles per voxel of the lattice's three faces) and
+// FieldSurfaceIndexed is called a second time only when a guess was short.
+func (e *Engine) SurfaceIndexed(scalarBuffer C.int, origin, step [3]float32, dims [3]int32, iso float32) (positions, normals []float32, indices []int32, err error) {
+	nx, ny, nz := int(dims[0]), int(dims[1]), int(dims[2])
+	area := nx*ny + ny*nz + nz*nx
+	capV, capT := 2*area, 4*area
+	if capV < 1024 {
+		capV = 1024
+	}
+	if capT < 1024 {
+		capT = 1024
+	}
+	for try := 0; try < 2; try++ {
+		positions = make([]float32, 3*capV)
+		normals = make([]float32, 3*capV)
+		indices = make([]int32, 3*capT)
+		v, t, err := e.FieldSurfaceIndexed(scalarBuffer, origin, step, dims, iso, positions, normals, indices)
+		if err != nil {
+			return nil, nil, nil, err
+		}
+		if int(v) <= capV && int(t) <= capT {
+			return positions[:3*int(v)], normals[:3*int(v)], indices[:3*int(t)], nil
+		}
+		if int(v) > capV {
+			capV = int(v)
+		}
+		if int(t) > capT {
+			capT = int(t)
+		}
+	}
+	return nil, nil, nil, errors.New("dslsph: SurfaceIndexed: the counts changed between two calls")
+}
+
 // ---- render hand-off without the per-step full read-back (pcisph_gpu_darwin.go:276-282) ----
 
 // DownloadDecimated: every stride-th particle of positions / velocities.
@@ -599,6 +679,8 @@ const (
 	// the last SurfaceExtract / FieldSurface: its triangles T, its bricks of 8 x 8 x 4 cubes with a triangle
 	OptSurfaceTriangles    = int(C.DSL_OPT_SURFACE_TRIANGLES)
 	OptSurfaceActiveBricks = int(C.DSL_OPT_SURFACE_ACTIVE_BRICKS)
+	// the last SurfaceExtractIndexed / FieldSurfaceIndexed: its vertices V
+	OptSurfaceVertices = int(C.DSL_OPT_SURFACE_VERTICES)
 )
 
 // SetOption / GetOption: library options (DSL_OPT_* in include/dslsph.h), e.g. the neighbour-list skin of WCSPHStep.

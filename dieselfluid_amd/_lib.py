@@ -106,6 +106,10 @@ EXPORTS = {
     "dsl_field_volume": (C.c_int, [_vp, C.c_int, _fp, _fp, _ip, _vp, _fp]),
     "dsl_surface_extract": (C.c_int, [_vp, _vp, _fp, _fp, _ip, C.c_float, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_int64)]),
     "dsl_field_surface": (C.c_int, [_vp, C.c_int, _fp, _fp, _ip, C.c_float, _fp, _fp, C.c_size_t, C.POINTER(C.c_int64)]),
+    "dsl_surface_extract_indexed": (C.c_int, [_vp, _vp, _fp, _fp, _ip, C.c_float, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp,
+                                              C.POINTER(C.c_int64)]),
+    "dsl_field_surface_indexed": (C.c_int, [_vp, C.c_int, _fp, _fp, _ip, C.c_float, _fp, _fp, C.c_size_t, _ip, C.c_size_t,
+                                            C.POINTER(C.c_int64)]),
     "dsl_wcsph_step": (C.c_int, [_vp, C.c_int]),
     "dsl_pcisph_begin": (C.c_int, [_vp]),
     "dsl_pcisph_step": (C.c_int, [_vp, C.c_int]),

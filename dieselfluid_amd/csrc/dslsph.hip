@@ -1794,7 +1794,12 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_SURFACE_ACTIVE_BRICKS:
     case DSL_OPT_SURFACE_COUNT_MS:
     case DSL_OPT_SURFACE_SCAN_MS:
-    case DSL_OPT_SURFACE_EMIT_MS: return surface_option(h, option, value);  // (blocking: the kernels count on the device)
+    case DSL_OPT_SURFACE_EMIT_MS:
+    case DSL_OPT_SURFACE_VERTICES:
+    case DSL_OPT_SURFACE_MESH_VCOUNT_MS:
+    case DSL_OPT_SURFACE_MESH_VSCAN_MS:
+    case DSL_OPT_SURFACE_MESH_VEMIT_MS:
+    case DSL_OPT_SURFACE_MESH_IEMIT_MS: return surface_option(h, option, value);  // (blocking: the kernels count on the device)
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }

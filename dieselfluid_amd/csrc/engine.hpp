@@ -7,6 +7,7 @@
 //   slab_link.hip      multi-GPU: communicator, slab link, re-balancing, the native slab step drivers
 //   volume.hip         field volumes: dsl_field_volume and its two kernels (a host unit with kernels of its own)
 //   surface.hip        fluid surfaces: dsl_surface_extract, dsl_field_surface and their four kernels (likewise)
+//   surface_mesh.hip   the indexed mesh: dsl_surface_extract_indexed, dsl_field_surface_indexed and their three kernels
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -189,6 +190,20 @@ struct dsl_handle {
   size_t surf_stage_count = 0;
   hipEvent_t surf_ev[5] = {};
   int surf_timed = 0;
+  // the indexed mesh (surface_mesh.hip; dsl_surface_extract_indexed).  mesh_words: one word per voxel, the voxel's vertex
+  // prefix inside its brick of 8 x 8 x 4 voxels << 7 | its 7-bit edge mask; mesh_scan: count, then offset, per voxel brick and
+  // the scan's upper levels; mesh_ctr: [0] vertices V of the last call; mesh_stage: dsl_field_surface_indexed's positions,
+  // normals and indices before they go to the host.  mesh_ev: vertex count | scan | vertex emit | index emit | while timing
+  // is on; mesh_timed: bit p = phase p was launched and marked
+  unsigned int* mesh_words = nullptr;
+  size_t mesh_words_count = 0;
+  unsigned long long* mesh_scan = nullptr;
+  size_t mesh_scan_count = 0;
+  unsigned long long* mesh_ctr = nullptr;
+  float* mesh_stage = nullptr;
+  size_t mesh_stage_count = 0;
+  hipEvent_t mesh_ev[8] = {};
+  int mesh_timed = 0;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -313,5 +328,39 @@ int field_volume_staged(dsl_handle* h, int scalar_buffer, const float origin[3],
 // ---- defined in surface.hip ----
 int surface_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SURFACE_* (get)
 void surface_free(dsl_handle* h);
+// ... and what surface_mesh.hip shares with it: the checked lattice of a call (nb: its bricks of 8 x 8 x 4 cubes, 0 without
+// cubes); the triangle count and scan into surf_scan / surf_ctr (T also to dev_count, or NULL); the levels of a scan over n
+// values and the array they take; the scan itself, one timing entry under kid; a blocking read of surf_ctr
+struct SurfLattice;
+int surf_lattice(dsl_handle* h, const char* who, const float* origin, const float* step, const int32_t* dims, SurfLattice* g,
+                 long long* nb);
+int surf_count(dsl_handle* h, const float* vol, const SurfLattice& g, long long nb, float iso, long long* dev_count);
+size_t surf_scan_layout(long long n, std::vector<long long>* len, std::vector<size_t>* first);
+int surf_scan_run(dsl_handle* h, int kid, unsigned long long* s, const std::vector<long long>& len, const std::vector<size_t>& first,
+                  unsigned long long* total_a, long long* total_b);
+int surf_read_ctr(dsl_handle* h, unsigned long long* two);
+
+// a library-owned device array that grows on demand and is counted in DSL_OPT_DEVICE_BYTES
+template <class T>
+int surf_reserve(dsl_handle* h, T** p, size_t* have, size_t want, const char* what) {
+  if (*have >= want) return DSL_OK;
+  (void)hipFree(*p);
+  h->dev_bytes -= *have * sizeof(T);
+  *p = nullptr;
+  *have = 0;
+  const hipError_t e = hipMalloc((void**)p, want * sizeof(T));
+  if (e != hipSuccess) {
+    *p = nullptr;
+    (void)hipGetLastError();  // (the handle stays usable: the next launch check must not meet this error)
+    return fail(h, DSL_ERR_NOMEM, std::string(what) + ": hipMalloc: " + hipGetErrorString(e));
+  }
+  *have = want;
+  h->dev_bytes += want * sizeof(T);
+  return DSL_OK;
+}
+
+// ---- defined in surface_mesh.hip ----
+int surface_mesh_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SURFACE_VERTICES and the mesh phases' ms (get)
+void surface_mesh_free(dsl_handle* h);
 
 }  // namespace dsl

@@ -21,7 +21,7 @@ _COMPS = {0: 3, 1: 3, 2: 3, 3: 1, 4: 1, 5: 3, 6: 3}
 KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
-    "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16,
+    "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16, "surface_mesh": 17,
 }
 
 
@@ -569,6 +569,44 @@ class SPHEngine:
             guess = n.value
         return verts[:n.value].copy(), norms[:n.value].copy()
 
+    def surface_extract_indexed(self, dev_volume, origin, step, dims, iso, dev_positions=None, dev_normals=None, cap_vertices: int = 0,
+                                dev_indices=None, cap_triangles: int = 0, dev_counts=None, want_counts: bool = True):
+        """The same surface as an indexed mesh (include/dslsph.h: dsl_surface_extract_indexed): every vertex once, a normal per
+        vertex, three int32 vertex ids per triangle.  Every dev_* argument is a device pointer (an int) or None: the first
+        min(V, cap_vertices) vertices go to dev_positions and dev_normals (3 floats each), the first min(T, cap_triangles)
+        triples to dev_indices, (V, T) to the two int64 at dev_counts.  Returns (V, T) (a blocking copy), or None with
+        want_counts = False: the call is then asynchronous on the engine's stream.  The mesh is complete only when both
+        capacities suffice."""
+        o, s, d = self._lattice(origin, step, dims)
+        n = (C.c_int64 * 2)(-1, -1)
+        self._ck(self._L.dsl_surface_extract_indexed(self._h, C.c_void_p(dev_volume), _fp(o), _fp(s), d.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     C.c_float(iso), C.c_void_p(dev_positions), C.c_void_p(dev_normals),
+                                                     int(cap_vertices), C.c_void_p(dev_indices), int(cap_triangles),
+                                                     C.c_void_p(dev_counts), n if want_counts else None))
+        return (int(n[0]), int(n[1])) if want_counts else None
+
+    def field_surface_indexed(self, origin, step, dims, iso, scalar: str = "densities", guess=(0, 0)):
+        """field_volume and the indexed mesh of it in one call: (V, 3) positions, (V, 3) normals and (T, 3) int32 indices.  The
+        host buffers are sized from a guess -- `guess` = (vertices, triangles), or two vertices and four triangles per voxel
+        of the lattice's three faces -- and the library is called again only when a guess was short."""
+        o, s, d = self._lattice(origin, step, dims)
+        ip = d.ctypes.data_as(C.POINTER(C.c_int32))
+        nx, ny, nz = (max(int(v), 1) for v in d)
+        area = nx * ny + ny * nz + nz * nx
+        cap_v = int(guess[0]) if guess[0] > 0 else max(1024, 2 * area)
+        cap_t = int(guess[1]) if guess[1] > 0 else max(1024, 4 * area)
+        n = (C.c_int64 * 2)(0, 0)
+        for _ in range(2):
+            pos = np.empty((cap_v, 3), dtype=np.float32)
+            nrm = np.empty((cap_v, 3), dtype=np.float32)
+            idx = np.empty((cap_t, 3), dtype=np.int32)
+            self._ck(self._L.dsl_field_surface_indexed(self._h, BUF[scalar], _fp(o), _fp(s), ip, C.c_float(iso), _fp(pos), _fp(nrm), cap_v,
+                                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), cap_t, n))
+            if n[0] <= cap_v and n[1] <= cap_t:
+                break
+            cap_v, cap_t = max(cap_v, int(n[0])), max(cap_t, int(n[1]))
+        return pos[:n[0]].copy(), nrm[:n[0]].copy(), idx[:n[1]].copy()
+
     # -- solver drivers -----------------------------------------------------------
     def wcsph_step(self, nsteps: int = 1):
         self._ck(self._L.dsl_wcsph_step(self._h, int(nsteps)))
@@ -605,7 +643,8 @@ class SPHEngine:
                "volume_bricks": 48, "volume_lds_bricks": 49, "volume_fallback_bricks": 50,
                "volume_empty_bricks": 51, "volume_staged_records": 52,
                "surface_triangles": 56, "surface_active_bricks": 57, "surface_count_ms": 58, "surface_scan_ms": 59,
-               "surface_emit_ms": 60}
+               "surface_emit_ms": 60, "surface_vertices": 61, "surface_mesh_vcount_ms": 62, "surface_mesh_vscan_ms": 63,
+               "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

@@ -342,6 +342,40 @@ class SPH {
     return m;
   }
 
+  // The same surface as an indexed mesh, what a renderer of indexed (glTF) meshes draws smooth-shaded: every vertex once
+  // with the volume's negated, normalised gradient as its normal, three vertex ids per triangle (include/dslsph.h:
+  // dsl_field_surface_indexed).  Triangle t is Indices[3 t .. 3 t + 2]; Positions[Indices[..]] are Surface()'s vertices.
+  struct IndexedMesh {
+    std::vector<mesh::Vec> Positions, Normals;  // V each
+    std::vector<int32_t> Indices;               // 3 T
+  };
+  IndexedMesh SurfaceIndexed(const float origin[3], const float step[3], const int32_t dims[3], float iso, bool density = true) {
+    const size_t area = (size_t)dims[0] * dims[1] + (size_t)dims[1] * dims[2] + (size_t)dims[2] * dims[0];
+    size_t cap_v = 2 * area < 1024 ? 1024 : 2 * area, cap_t = 4 * area < 1024 ? 1024 : 4 * area;
+    std::vector<float> pos, normals;
+    IndexedMesh m;
+    int64_t counts[2] = {0, 0};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      pos.resize(3 * cap_v);
+      normals.resize(3 * cap_v);
+      m.Indices.resize(3 * cap_t);
+      ck(dsl_field_surface_indexed(h_, density ? DSL_BUF_DENSITIES : DSL_BUF_PRESSURES, origin, step, dims, iso, pos.data(),
+                                   normals.data(), cap_v, m.Indices.data(), cap_t, counts));
+      if ((size_t)counts[0] <= cap_v && (size_t)counts[1] <= cap_t) break;
+      if ((size_t)counts[0] > cap_v) cap_v = (size_t)counts[0];
+      if ((size_t)counts[1] > cap_t) cap_t = (size_t)counts[1];
+    }
+    const size_t V = (size_t)counts[0];
+    m.Indices.resize(3 * (size_t)counts[1]);
+    m.Positions.resize(V);
+    m.Normals.resize(V);
+    for (size_t v = 0; v < V; ++v) {
+      m.Positions[v] = {pos[3 * v], pos[3 * v + 1], pos[3 * v + 2]};
+      m.Normals[v] = {normals[3 * v], normals[3 * v + 1], normals[3 * v + 2]};
+    }
+    return m;
+  }
+
   int N() const { return particles_; }                 // fluid.go:106-108
   void NN() { ck(dsl_build_neighbours(h_)); }          // fluid.go:100-102
   float CFL() {                                        // fluid.go:111-114

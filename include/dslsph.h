@@ -153,7 +153,8 @@ enum {
   DSL_K_COLLIDE = 14,     /* triangle-mesh collider: query + response (only while a mesh is set) */
   DSL_K_VOLUME = 15,      /* dsl_field_volume: the lattice sweep, either form */
   DSL_K_SURFACE = 16,     /* dsl_surface_extract: its count, scan and emit launches, one entry each */
-  DSL_K_COUNT = 17
+  DSL_K_SURFACE_MESH = 17, /* dsl_surface_extract_indexed: its vertex count, vertex scan, vertex emit and index emit */
+  DSL_K_COUNT = 18
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -312,6 +313,64 @@ int dsl_surface_extract(dsl_handle *h, const float *dev_volume, const float orig
 int dsl_field_surface(dsl_handle *h, int scalar_buffer, const float origin[3], const float step[3], const int32_t dims[3],
                       float iso, float *host_vertices, float *host_normals, size_t cap_triangles,
                       int64_t *n_triangles);
+
+/* Fluid surfaces as an INDEXED mesh: the same surface as dsl_surface_extract's, with every vertex stored once, a normal per
+ * vertex, and three int32 vertex ids per triangle -- what a renderer of indexed meshes (glTF) draws, smooth-shaded, without
+ * a welding pass on the host.  Lattice, cubes, Kuhn tetrahedra, the inside test (value >= iso), the non-finite rule, the
+ * triangle count T, the triangle order and the winding are exactly dsl_surface_extract's; the rule for the rest is
+ * build-defined too:
+ *
+ * Vertices.  Every edge of the Kuhn triangulation is a translate of one of seven types: for a voxel u and d in 1..7, edge
+ * (u, d) runs from u to w = u + (d & 1, (d >> 1) & 1, (d >> 2) & 1); u is the end with the smaller linear index.  A vertex
+ * exists on edge (u, d) iff w is inside the lattice, exactly one of u, w is inside the surface, and at least one LIVE cube
+ * holds both ends -- the cubes with corner 0 at u - s for the offsets s in 0..7 with (s & d) == 0; a cube is live when it
+ * lies within the lattice and its 8 corners are finite.  That is exactly the set of edges some triangle touches: every
+ * vertex is referenced, every reference has a vertex.  At a voxel that equals iso several vertices share their position
+ * bits; they stay distinct vertices, so the mesh welded by id is a manifold where the soup welded by bits is not.
+ * Position: dsl_surface_extract's edge point, f = (iso - v_u) / (v_w - v_u), p = x_u + f * (x_w - x_u), the same bits:
+ * positions[indices[3 * t + e]] is vertex e of the soup's triangle t, bit for bit.
+ * Vertex order: bricks of 8 x 8 x 4 VOXELS ascending, x fastest, the first at voxel 0 -- ceil(nx / 8) * ceil(ny / 8) *
+ * ceil(nz / 4) of them, which can be one more per axis than the bricks of cubes; inside a brick its voxels ascending, x
+ * fastest; inside a voxel d ascending.  Every id comes from counts and a prefix sum, none from an atomic.
+ * Normal: the negated gradient of the volume at the vertex, towards lower values like the triangles' normals.  Per voxel p
+ * and axis a, with x dsl_field_volume's coordinate: p - e_a is usable when it lies inside the lattice and its value is
+ * finite, p + e_a likewise; both usable: g_a = (v+ - v-) / (x+ - x-); only +: (v+ - v_p) / (x+ - x_p); only -:
+ * (v_p - v-) / (x_p - x-); neither: 0.  At the vertex G_a = g_a(u) + f * (g_a(w) - g_a(u)) with the position's f,
+ * len = sqrt((Gx^2 + Gy^2) + Gz^2), n = (-G) / len, or (0, 0, 0) when len is not > 0.  float32, every difference, product,
+ * sum and quotient rounded once, IEEE division and square root, nothing fused: the same bits in both math modes.
+ * Limit: at most 2^28 voxels, so that every id (< 7 * 2^28) is a non-negative int32.
+ *
+ * dsl_surface_extract_indexed reads dev_volume and no particle state: it does not settle a live skin episode and works on
+ * slab handles.  It writes the first min(V, cap_vertices) vertices to dev_positions (3 floats each) and, unless NULL, to
+ * dev_normals (3 floats each), the first min(T, cap_triangles) index triples to dev_indices, and nothing beyond them.  V and
+ * T are the full numbers whatever the capacities: dev_counts (two int64 of device memory, unless NULL) and host_counts take
+ * [0] = V, [1] = T.  Asynchronous on the handle's stream unless host_counts is given (a blocking copy).  Capacities of 0 with
+ * NULL outputs make the counting call.  A written triple may name a vertex >= cap_vertices: THE MESH IS COMPLETE ONLY WHEN
+ * BOTH CAPACITIES SUFFICE (cap_vertices >= V and cap_triangles >= T).
+ * Memory: besides dsl_surface_extract's 8 bytes per brick of cubes the library keeps one 32-bit word PER VOXEL -- as much as
+ * the volume itself -- and 8 bytes per brick of voxels, all of its own, grown on demand, counted in DSL_OPT_DEVICE_BYTES
+ * and freed by dsl_destroy.
+ * DSL_ERR_INVALID (dsl_last_error names the argument): dsl_surface_extract's refusals (dev_volume NULL, a dims entry < 1, a
+ * step entry that is not finite and > 0, a non-finite origin or iso), more than 2^28 voxels in dims, cap_vertices > 0 with
+ * dev_positions NULL, cap_triangles > 0 with dev_indices NULL.  A refused call touches nothing.
+ *
+ * dsl_field_surface_indexed is to it what dsl_field_surface is to dsl_surface_extract: dsl_field_volume into the library's
+ * staging array, count and scan, a blocking read of the counts, the emits into an array of the library's own grown to
+ * min(V, cap_vertices) and min(T, cap_triangles), and blocking copies; counts[0] = V, counts[1] = T (counts may be NULL).
+ * Refusals and slab behaviour (DSL_ERR_UNSUPPORTED) are dsl_field_volume's, plus a non-finite iso, more than 2^28 voxels,
+ * cap_vertices > 0 with host_positions NULL and cap_triangles > 0 with host_indices NULL; it settles a live skin episode.
+ *
+ * The triangle count and its scan are dsl_surface_extract's own launches, timed under DSL_K_SURFACE; the vertex count, the
+ * vertex scan, the vertex emit and the index emit are timed under DSL_K_SURFACE_MESH, one entry each.
+ * DSL_OPT_SURFACE_VERTICES is V of the last indexed call; DSL_OPT_SURFACE_TRIANGLES its T. */
+int dsl_surface_extract_indexed(dsl_handle *h, const float *dev_volume, const float origin[3], const float step[3],
+                                const int32_t dims[3], float iso, float *dev_positions /* 3 per vertex */,
+                                float *dev_normals /* 3 per vertex, or NULL */, size_t cap_vertices,
+                                int32_t *dev_indices /* 3 per triangle */, size_t cap_triangles,
+                                int64_t *dev_counts /* [0] = V, [1] = T; or NULL */, int64_t *host_counts /* likewise */);
+int dsl_field_surface_indexed(dsl_handle *h, int scalar_buffer, const float origin[3], const float step[3],
+                              const int32_t dims[3], float iso, float *host_positions, float *host_normals,
+                              size_t cap_vertices, int32_t *host_indices, size_t cap_triangles, int64_t counts[2]);
 
 /* Step drivers: one iteration of WCSPH.Run (solver/wcsph/wcsph.go:14-26) and of
  * PciMethod.Run (solver/pcisph/pcisph_darwin.go:43-101) per step.  Asynchronous: they
@@ -720,7 +779,13 @@ enum {
   DSL_OPT_SURFACE_ACTIVE_BRICKS = 57,  /* (get, blocking) bricks of 8 x 8 x 4 cubes that emitted at least one triangle */
   DSL_OPT_SURFACE_COUNT_MS = 58,       /* (get, blocking) milliseconds of its count launch, from device events recorded while */
   DSL_OPT_SURFACE_SCAN_MS = 59,        /* dsl_timing_enable(1) holds (0 otherwise); its scan launches; */
-  DSL_OPT_SURFACE_EMIT_MS = 60         /* its emit launch (0 for a call that emitted nothing) */
+  DSL_OPT_SURFACE_EMIT_MS = 60,        /* its emit launch (0 for a call that emitted nothing) */
+  /* dsl_surface_extract_indexed / dsl_field_surface_indexed, the last call's */
+  DSL_OPT_SURFACE_VERTICES = 61,           /* (get, blocking) V, the full number of vertices */
+  DSL_OPT_SURFACE_MESH_VCOUNT_MS = 62,     /* (get, blocking) milliseconds of its vertex count launch, as DSL_OPT_SURFACE_COUNT_MS; */
+  DSL_OPT_SURFACE_MESH_VSCAN_MS = 63,      /* its vertex scan launches; */
+  DSL_OPT_SURFACE_MESH_VEMIT_MS = 64,      /* its vertex emit launch (0 for a call with cap_vertices = 0 or V = 0); */
+  DSL_OPT_SURFACE_MESH_IEMIT_MS = 65       /* its index emit launch (0 for a call with cap_triangles = 0 or without cubes) */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
