@@ -916,3 +916,67 @@ func (e *Engine) ColliderQueryInto(tri []int32, normal, coord, point []float32) 
 	}
 	return e.ck(C.dsl_collider_query(e.h, tp, fp(normal), fp(coord), fp(point)))
 }
+
+// ---- implicit colliders: the distance volume of a mesh, collision against a distance volume (include/dslsph.h) ----
+
+const (
+	// flags of MeshDistanceVolume and SetColliderVolume: distances without a sign (an open mesh, a thin shell)
+	SdfUnsigned = int(C.DSL_SDF_UNSIGNED)
+	// the timing id of MeshDistanceVolume's launches (dsl_timing_get)
+	KSdf = int(C.DSL_K_SDF)
+	// the last MeshDistanceVolume: its bricks of 8 x 8 x 4 voxels with a triangle list, the (voxel, triangle) pairs tested,
+	// the milliseconds of its distance and sign phases (while timing is on); the voxels of the volume collider (0: none)
+	OptSdfActiveBricks = int(C.DSL_OPT_SDF_ACTIVE_BRICKS)
+	OptSdfVisits       = int(C.DSL_OPT_SDF_VISITS)
+	OptSdfDistanceMs   = int(C.DSL_OPT_SDF_DISTANCE_MS)
+	OptSdfSignMs       = int(C.DSL_OPT_SDF_SIGN_MS)
+	OptColliderVolume  = int(C.DSL_OPT_COLLIDER_VOLUME)
+)
+
+// MeshDistanceVolume: the signed distance (negative inside; flags = SdfUnsigned: no sign) of every point of the lattice
+// origin + step * (i, j, k) to the triangles (9 floats each), cut off at band (+Inf: no cut), x fastest.  devOut (device
+// memory, dims[0]*dims[1]*dims[2] floats, written on the engine's stream) and hostOut (as many floats, blocking) may each
+// be nil, not both.
+func (e *Engine) MeshDistanceVolume(vertices []float32, origin, step [3]float32, dims [3]int32, band float32, flags int, devOut unsafe.Pointer, hostOut []float32) error {
+	if len(vertices) == 0 || len(vertices)%9 != 0 {
+		return errors.New("MeshDistanceVolume: 9 vertex floats per triangle, at least one triangle")
+	}
+	var hp *C.float
+	if len(hostOut) > 0 {
+		if len(hostOut) < int(dims[0])*int(dims[1])*int(dims[2]) {
+			return errors.New("MeshDistanceVolume: hostOut is shorter than the lattice")
+		}
+		hp = (*C.float)(unsafe.Pointer(&hostOut[0]))
+	}
+	return e.ck(C.dsl_mesh_distance_volume(e.h, (*C.float)(unsafe.Pointer(&vertices[0])), C.size_t(len(vertices)/9), (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])), (*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(band), C.int(flags), (*C.float)(devOut), hp))
+}
+
+// SetColliderVolume: a distance volume as the collider of the step -- devVolume (device memory) or hostVolume, exactly one
+// of them; the library keeps a copy.  A particle closer than radius to the surface is pushed out along the volume's
+// gradient and reflected.  It excludes a collider mesh.  RemoveColliderVolume removes it.
+func (e *Engine) SetColliderVolume(devVolume unsafe.Pointer, hostVolume []float32, origin, step [3]float32, dims [3]int32, radius, restitution float32, flags int) error {
+	var hp *C.float
+	if len(hostVolume) > 0 {
+		if len(hostVolume) < int(dims[0])*int(dims[1])*int(dims[2]) {
+			return errors.New("SetColliderVolume: hostVolume is shorter than the lattice")
+		}
+		hp = (*C.float)(unsafe.Pointer(&hostVolume[0]))
+	}
+	return e.ck(C.dsl_collider_set_volume(e.h, (*C.float)(devVolume), hp, (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])), (*C.int32_t)(unsafe.Pointer(&dims[0])), C.float(radius), C.float(restitution), C.int(flags)))
+}
+
+func (e *Engine) RemoveColliderVolume() error {
+	return e.ck(C.dsl_collider_set_volume(e.h, nil, nil, nil, nil, nil, 0, 0, 0))
+}
+
+// ColliderVolumeQuery: the interpolated distance (N) and the unit gradient (3 N) of the volume collider at every fluid
+// particle in host order, no response (blocking); zeros where a particle lies in no cell of the volume.
+func (e *Engine) ColliderVolumeQuery() (dist, normal []float32, err error) {
+	n := int(e.Params.n_particles)
+	dist, normal = make([]float32, n), make([]float32, 3*n)
+	if n == 0 {
+		return
+	}
+	err = e.ck(C.dsl_collider_volume_query(e.h, (*C.float)(unsafe.Pointer(&dist[0])), (*C.float)(unsafe.Pointer(&normal[0]))))
+	return
+}

@@ -116,6 +116,9 @@ EXPORTS = {
     "dsl_collider_set_mesh": (C.c_int, [_vp, _fp, _fp, C.c_size_t, C.c_float, C.c_float]),
     "dsl_collide_pass": (C.c_int, [_vp]),
     "dsl_collider_query": (C.c_int, [_vp, _ip, _fp, _fp, _fp]),
+    "dsl_mesh_distance_volume": (C.c_int, [_vp, _fp, C.c_size_t, _fp, _fp, _ip, C.c_float, C.c_int, _vp, _fp]),
+    "dsl_collider_set_volume": (C.c_int, [_vp, _vp, _fp, _fp, _fp, _ip, C.c_float, C.c_float, C.c_int]),
+    "dsl_collider_volume_query": (C.c_int, [_vp, _fp, _fp]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

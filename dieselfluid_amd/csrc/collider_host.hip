@@ -267,6 +267,7 @@ int collide_pass_slab(dsl_handle* h) {
 
 namespace dsl {
 int collide_pass(dsl_handle* h) {
+  if (h->colv_on) return collide_volume_pass(h);  // (a volume collider excludes a mesh: sdf.hip)
   if (h->col_tri == 0) return DSL_OK;
   if (h->c.n_ptr) return collide_pass_slab(h);
   HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
@@ -295,6 +296,9 @@ int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* nor
     col_index_free(h);
     return DSL_OK;
   }
+  if (h->colv_on)
+    return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: a volume collider is set, and a mesh collider and a volume collider exclude "
+                                    "each other; remove the volume first (dsl_collider_set_volume with dims = NULL)");
   if (!vertices || !normals) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: null vertex or normal pointer");
   if (n_triangles > ((size_t)1 << 24)) return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: more than 2^24 triangles");
   const int T = (int)n_triangles, nchunk = (T + kColChunk - 1) / kColChunk;

@@ -777,6 +777,7 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->vol_stage);
   (void)hipFree(h->vol_ctr);
   surface_free(h);
+  sdf_free(h);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1459,7 +1460,7 @@ constexpr int kSkinRetry = 2048;
 
 bool skin_usable(const dsl_handle* h) {
   return h->skin > 0.0f && h->steps >= h->skin_retry_at && h->prm.math_mode == DSL_MATH_FAST && !h->lsh && h->c.slab_axis < 0 && !h->c.n_ptr && h->nb == 0 &&
-         h->col_tri == 0 &&  // (the collide pass moves particles behind the kernel that measures displacement)
+         h->col_tri == 0 && !h->colv_on &&  // (the collide pass moves particles behind the kernel that measures displacement)
          !h->pci_active && h->c.xsph_eps == 0.0f && h->c.st_kappa == 0.0f && use_tiled(h) && h->nmask != nullptr &&
          (h->c.wcsph_pressure_force != 0 || h->c.wcsph_viscosity != 0);
 }
@@ -1637,7 +1638,7 @@ int dsl_wcsph_step(dsl_handle* h, int nsteps) {
     if (int rc = build_grid(h, false)) return rc;  // NN(): geometric neighbour rule -> every step
     if (int rc = density_pass(h)) return rc;        // DensityAll   wcsph.go:18
     if (int rc = force_integrate(h)) return rc;     // ExternalAll, PressureAll, Update wcsph.go:19-21
-    if (int rc = collide_pass(h)) return rc;        // (only while a collider mesh is set)
+    if (int rc = collide_pass(h)) return rc;        // (only while a collider mesh or volume is set)
     h->steps++;
   }
   return DSL_OK;
@@ -1800,6 +1801,11 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_SURFACE_MESH_VSCAN_MS:
     case DSL_OPT_SURFACE_MESH_VEMIT_MS:
     case DSL_OPT_SURFACE_MESH_IEMIT_MS: return surface_option(h, option, value);  // (blocking: the kernels count on the device)
+    case DSL_OPT_SDF_ACTIVE_BRICKS:
+    case DSL_OPT_SDF_VISITS:
+    case DSL_OPT_SDF_DISTANCE_MS:
+    case DSL_OPT_SDF_SIGN_MS:
+    case DSL_OPT_COLLIDER_VOLUME: return sdf_option(h, option, value);  // (blocking but the last)
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }
@@ -2030,7 +2036,7 @@ int pci_check(dsl_handle* h) {                   // :95-98
 
 int pci_end_step(dsl_handle* h) {                // Update :101 (positions advect with v + XSPH)
   if (int rc = update_pass(h, pci_extra_terms(h))) return rc;
-  if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh is set)
+  if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh or volume is set)
   h->steps++;
   h->pci_steps++;
   return DSL_OK;
@@ -2104,6 +2110,7 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (h->lsh) return fail(h, DSL_ERR_UNSUPPORTED, "lsh_ref buckets are angular cones through the whole domain: no slabs");
   if (axis >= 0 && h->nb > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: boundary particles are not supported in slab mode");
   if (axis >= 0 && h->col_tri > 0 && !h->col_slab) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
+  if (axis >= 0 && h->colv_on) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a volume collider is not supported in slab mode");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;

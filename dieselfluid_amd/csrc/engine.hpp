@@ -8,6 +8,7 @@
 //   volume.hip         field volumes: dsl_field_volume and its two kernels (a host unit with kernels of its own)
 //   surface.hip        fluid surfaces: dsl_surface_extract, dsl_field_surface and their four kernels (likewise)
 //   surface_mesh.hip   the indexed mesh: dsl_surface_extract_indexed, dsl_field_surface_indexed and their three kernels
+//   sdf.hip            implicit colliders: dsl_mesh_distance_volume, dsl_collider_set_volume, the volume collide pass, their kernels
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -204,6 +205,38 @@ struct dsl_handle {
   size_t mesh_stage_count = 0;
   hipEvent_t mesh_ev[8] = {};
   int mesh_timed = 0;
+  // distance volumes of a mesh (sdf.hip; dsl_mesh_distance_volume), all allocated on first use and grown on demand.  sdf_stage:
+  // the output of a host_out-only call; sdf_verts: the caller's vertices; sdf_rec / sdf_box: four float4 and six floats per
+  // triangle; sdf_scan: one count, then offset, per brick of 8 x 8 x 4 voxels and the scan's upper levels; sdf_list: the
+  // bricks' triangle lists; sdf_marks: one word per voxel, the sign sweep's marks; sdf_ctr: [0] bricks with a list, [1] triangle
+  // visits, [2] list entries of the last call.  sdf_ev: | distance | . | sign | while timing is on; sdf_timed: 0 none, 1 distance, 2 both
+  float* sdf_stage = nullptr;
+  size_t sdf_stage_count = 0;
+  float* sdf_verts = nullptr;
+  size_t sdf_verts_count = 0;
+  float4* sdf_rec = nullptr;
+  size_t sdf_rec_count = 0;
+  float* sdf_box = nullptr;
+  size_t sdf_box_count = 0;
+  unsigned long long* sdf_scan = nullptr;
+  size_t sdf_scan_count = 0;
+  int* sdf_list = nullptr;
+  size_t sdf_list_count = 0;
+  unsigned int* sdf_marks = nullptr;
+  size_t sdf_marks_count = 0;
+  unsigned long long* sdf_ctr = nullptr;
+  hipEvent_t sdf_ev[4] = {};
+  int sdf_timed = 0;
+  // the volume collider (sdf.hip; dsl_collider_set_volume): the library's copy of the volume and its lattice.  colv_on: set --
+  // the collide pass runs k_collide_volume and a mesh is refused; colv_query: dsl_collider_volume_query's staging (4 words per particle)
+  float* colv_vol = nullptr;
+  size_t colv_count = 0;
+  bool colv_on = false;
+  float colv_o[3] = {}, colv_s[3] = {};
+  int colv_n[3] = {};
+  float colv_radius = 0.0f, colv_rest = 0.0f;
+  int colv_flags = 0;
+  float* colv_query = nullptr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -362,5 +395,10 @@ int surf_reserve(dsl_handle* h, T** p, size_t* have, size_t want, const char* wh
 // ---- defined in surface_mesh.hip ----
 int surface_mesh_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SURFACE_VERTICES and the mesh phases' ms (get)
 void surface_mesh_free(dsl_handle* h);
+
+// ---- defined in sdf.hip ----
+int sdf_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SDF_* and DSL_OPT_COLLIDER_VOLUME (get)
+void sdf_free(dsl_handle* h);
+int collide_volume_pass(dsl_handle* h);  // the collide pass while a volume collider is set
 
 }  // namespace dsl

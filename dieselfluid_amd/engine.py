@@ -21,8 +21,9 @@ _COMPS = {0: 3, 1: 3, 2: 3, 3: 1, 4: 1, 5: 3, 6: 3}
 KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
-    "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16, "surface_mesh": 17,
+    "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16, "surface_mesh": 17, "sdf": 18,
 }
+SDF_UNSIGNED = 1  # DSL_SDF_UNSIGNED
 
 
 def _fp(a):
@@ -490,6 +491,54 @@ class SPHEngine:
                                             _fp(point)))
         return tri, nrm, coord, point
 
+    # -- implicit colliders (include/dslsph.h: dsl_mesh_distance_volume, dsl_collider_set_volume) --
+    def mesh_distance_volume(self, vertices, origin, step, dims, band: float = float("inf"), unsigned: bool = False, dev_out=None):
+        """The signed (or unsigned) distance of every lattice point origin + step * (i, j, k) to the triangles `vertices`
+        (T, 3, 3), cut off at `band`: an ndarray of shape (nz, ny, nx), or None with `dev_out` -- a device pointer to
+        nx * ny * nz floats, written on the engine's stream.  Negative inside (the +x ray crosses an odd number of triangles)."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1)
+        if v.size % 9:
+            raise DslError("mesh_distance_volume: 9 vertex floats per triangle")
+        o, s, d = self._lattice(origin, step, dims)
+        ip = d.ctypes.data_as(C.POINTER(C.c_int32))
+        flags = SDF_UNSIGNED if unsigned else 0
+        if dev_out is not None:
+            self._ck(self._L.dsl_mesh_distance_volume(self._h, _fp(v), v.size // 9, _fp(o), _fp(s), ip, C.c_float(band), flags,
+                                                      C.c_void_p(dev_out), None))
+            return None
+        n = int(d[0]) * int(d[1]) * int(d[2])
+        out = np.empty(n if d.min() >= 1 and n <= 1 << 30 else 1, dtype=np.float32)  # (dims the library refuses: _ck raises)
+        self._ck(self._L.dsl_mesh_distance_volume(self._h, _fp(v), v.size // 9, _fp(o), _fp(s), ip, C.c_float(band), flags, None,
+                                                  _fp(out)))
+        return out.reshape(int(d[2]), int(d[1]), int(d[0]))
+
+    def set_collider_volume(self, volume=None, origin=None, step=None, dims=None, radius: float = 0.0, restitution: float = 0.0,
+                            unsigned: bool = False, dev_volume=None):
+        """A distance volume as the step's collider: `volume` an array of shape (nz, ny, nx), or `dev_volume` a device pointer
+        with `dims` = (nx, ny, nz); the library keeps a copy.  Neither (or dims None without an array) removes the collider."""
+        flags = SDF_UNSIGNED if unsigned else 0
+        if volume is None and dev_volume is None:
+            self._ck(self._L.dsl_collider_set_volume(self._h, None, None, None, None, None, C.c_float(0), C.c_float(0), 0))
+            return
+        if volume is not None:
+            vol = np.ascontiguousarray(volume, dtype=np.float32)
+            if vol.ndim != 3:
+                raise DslError("set_collider_volume: volume has the shape (nz, ny, nx)")
+            dims = vol.shape[::-1]
+        o, s, d = self._lattice(origin, step, dims)
+        ip = d.ctypes.data_as(C.POINTER(C.c_int32))
+        self._ck(self._L.dsl_collider_set_volume(self._h, C.c_void_p(dev_volume) if volume is None else None,
+                                                 _fp(vol) if volume is not None else None, _fp(o), _fp(s), ip,
+                                                 C.c_float(radius), C.c_float(restitution), flags))
+
+    def collider_volume_query(self):
+        """the interpolated distance and the unit gradient of the volume collider at every fluid particle, host order, no response"""
+        n = self.n_fluid
+        dist = np.empty(n, dtype=np.float32)
+        nrm = np.empty((n, 3), dtype=np.float32)
+        self._ck(self._L.dsl_collider_volume_query(self._h, _fp(dist), _fp(nrm)))
+        return dist, nrm
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -644,7 +693,8 @@ class SPHEngine:
                "volume_empty_bricks": 51, "volume_staged_records": 52,
                "surface_triangles": 56, "surface_active_bricks": 57, "surface_count_ms": 58, "surface_scan_ms": 59,
                "surface_emit_ms": 60, "surface_vertices": 61, "surface_mesh_vcount_ms": 62, "surface_mesh_vscan_ms": 63,
-               "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65}
+               "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65,
+               "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

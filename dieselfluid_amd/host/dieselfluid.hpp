@@ -317,6 +317,48 @@ class SPH {
     ck(dsl_collider_set_mesh(h_, verts.data(), normals.data(), normals.size() / 3, r, e));
   }
 
+  // Implicit colliders (README.MD:35-37 "SPH/Fluid Implicit Collision Techniques / SDF Processing"; the collider interface
+  // "for SDF representation", render/mesh/collider.go:10-36): the signed distance of every point of the lattice
+  // origin + step * (i, j, k) to a mesh, negative inside, cut off at `band`, computed on the device
+  // (include/dslsph.h: dsl_mesh_distance_volume).  Values are x fastest.
+  struct DistanceVolume {
+    float origin[3] = {0.f, 0.f, 0.f}, step[3] = {1.f, 1.f, 1.f};
+    int32_t dims[3] = {0, 0, 0};
+    bool isUnsigned = false;
+    std::vector<float> Values;
+    float At(int i, int j, int k) const { return Values[((size_t)k * dims[1] + j) * dims[0] + i]; }
+  };
+  DistanceVolume MeshDistance(const mesh::Mesh& m, const float origin[3], const float step[3], const int32_t dims[3],
+                              float band = INFINITY, bool isUnsigned = false) {
+    DistanceVolume v;
+    std::vector<float> verts;
+    for (const mesh::Vec& p : m.Vertexes) verts.insert(verts.end(), p.begin(), p.end());
+    for (int a = 0; a < 3; ++a) v.origin[a] = origin[a], v.step[a] = step[a], v.dims[a] = dims[a];
+    v.isUnsigned = isUnsigned;
+    if (dims[0] > 0 && dims[1] > 0 && dims[2] > 0) v.Values.resize((size_t)dims[0] * dims[1] * dims[2]);
+    ck(dsl_mesh_distance_volume(h_, verts.data(), verts.size() / 9, origin, step, dims, band, isUnsigned ? DSL_SDF_UNSIGNED : 0,
+                                nullptr, v.Values.data()));
+    return v;
+  }
+  // A collider that wraps a distance volume: a particle closer than `Radius` to the surface is pushed out along the
+  // volume's gradient and reflected with `Restitution` (include/dslsph.h: dsl_collider_set_volume).  Any volume will do,
+  // MeshDistance's or one the host filled in.  It excludes a mesh list: set one or the other.
+  struct VolumeCollider {
+    DistanceVolume Volume;
+    float Radius = 0.f, Restitution = 0.f;
+  };
+  void Collider(const VolumeCollider& c) {
+    ck(dsl_collider_set_volume(h_, nullptr, c.Volume.Values.data(), c.Volume.origin, c.Volume.step, c.Volume.dims, c.Radius,
+                               c.Restitution, c.Volume.isUnsigned ? DSL_SDF_UNSIGNED : 0));
+  }
+  void RemoveVolumeCollider() { ck(dsl_collider_set_volume(h_, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0)); }
+  // distance and unit gradient of the volume collider at every fluid particle (dsl_collider_volume_query)
+  void ColliderDistances(std::vector<float>* dist, std::vector<float>* normal) {
+    if (dist) dist->resize((size_t)particles_);
+    if (normal) normal->resize(3 * (size_t)particles_);
+    ck(dsl_collider_volume_query(h_, dist ? dist->data() : nullptr, normal ? normal->data() : nullptr));
+  }
+
   // The fluid's surface as a mesh.Mesh (README.MD:38 "SPH/Fluid Surfaces"; the reference's renderer draws meshes): the
   // iso-surface of SPHField.Interpolate on the lattice origin + step * (i, j, k), evaluated, triangulated and wound on the
   // device (include/dslsph.h: dsl_field_surface).  density = false: the pressure field.  The buffer is sized from a guess --

@@ -154,7 +154,8 @@ enum {
   DSL_K_VOLUME = 15,      /* dsl_field_volume: the lattice sweep, either form */
   DSL_K_SURFACE = 16,     /* dsl_surface_extract: its count, scan and emit launches, one entry each */
   DSL_K_SURFACE_MESH = 17, /* dsl_surface_extract_indexed: its vertex count, vertex scan, vertex emit and index emit */
-  DSL_K_COUNT = 18
+  DSL_K_SDF = 18,          /* dsl_mesh_distance_volume: prep, brick count, scan, brick fill, distance, sweep, sign, one entry each */
+  DSL_K_COUNT = 19
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -473,6 +474,70 @@ int dsl_collide_pass(dsl_handle *h);
 int dsl_collider_query(dsl_handle *h, int32_t *tri /* N: index or -1 */, float *normal /* 3N */,
                        float *coord /* 3N */, float *point /* 3N */);
 
+/* ---- implicit colliders: the distance volume of a triangle mesh, and collision against a distance volume (csrc/sdf.hip) ----
+ * The reference names them ("SPH/Fluid Implicit Collision Techniques / SDF Processing", README.MD:35-39; colliders "for SDF
+ * representation", render/mesh/collider.go:10-36) and implements neither: both rules below are BUILD-DEFINED, like the wall
+ * box.  They are float32 with every operation rounded once and nothing fused, a dot product is (x*x + y*y) + z*z, divisions
+ * and square roots are correctly rounded, and they are the same in DSL_MATH_EXACT and DSL_MATH_FAST.  tests/sdf_ref.py
+ * restates them operation for operation.
+ *
+ * dsl_mesh_distance_volume: the lattice, coordinates (origin + step * (float)idx, each operation rounded once), output order
+ * (x fastest) and dev_out / host_out behaviour are dsl_field_volume's: dev_out is written on the handle's stream, host_out is
+ * blocking, with host_out alone the library stages in an array of its own (DSL_OPT_DEVICE_BYTES).  The call itself blocks
+ * once, for the length of its brick lists; `vertices` (T triangles a, b, c, host memory) is not retained.  It reads no
+ * particle state, does not settle a live skin episode and works on slab handles.
+ *   Distance.  Per triangle d2 is the squared distance of the voxel p to the closest point q of the triangle, by the seven
+ *   regions on d1 = ab.(p-a), d2 = ac.(p-a), d3 = ab.(p-b), d4 = ac.(p-b), d5 = ab.(p-c), d6 = ac.(p-c), the first that holds:
+ *     d1 <= 0 and d2 <= 0: q = a;   d3 >= 0 and d4 <= d3: q = b;   d6 >= 0 and d5 <= d6: q = c;
+ *     vc = d1 d4 - d3 d2 <= 0, d1 >= 0, d3 <= 0: q = a + ab (d1 / (d1 - d3));
+ *     vb = d5 d2 - d1 d6 <= 0, d2 >= 0, d6 <= 0: q = a + ac (d2 / (d2 - d6));
+ *     va = d3 d6 - d5 d4 <= 0, e1 = d4 - d3 >= 0, e2 = d5 - d6 >= 0: q = b + (c - b) (e1 / (e1 + e2));
+ *     else s = (va + vb) + vc, q = (a + ab (vb / s)) + ac (vc / s);
+ *   d2 = |p - q|^2.  A triangle whose d2 is not finite (a degenerate triangle that divides zero by zero) never wins.  The
+ *   value is min(sqrt(min_t d2), band): far voxels hold exactly `band`.  The minimum does not depend on the order, so the
+ *   broad phase (bricks of 8 x 8 x 4 voxels list the triangles whose box, inflated by the band, reaches them) gives the
+ *   brute-force bits.
+ *   Sign (flags & DSL_SDF_UNSIGNED == 0).  A voxel is inside when the ray from it towards +x crosses an odd number of
+ *   triangles; the value is inside ? -d : d.  No normals, no orientation.  Projected onto (y, z): per edge of a triangle,
+ *   its ends ordered by (y, then z) are lo and hi, delta = hi - lo, E(q) = delta.y (q.z - lo.z) - delta.z (q.y - lo.y).  A
+ *   triangle is skipped when an edge has delta = 0 or E(r) is not > 0 or < 0 for the opposite vertex r.  The ray of the row
+ *   (y, z) belongs to the triangle when y and z lie within the vertices' smallest and largest y and z and, for all three
+ *   edges, sgn E(row) = sgn E(r), E(row) == 0 read as + when delta.z <= 0 and as - when delta.z > 0 (one infinitesimal shift
+ *   of every ray: exactly one of two triangles across an edge claims a ray through it).  The crossing lies at
+ *   x_hit = a.x - (n.y (y - a.y) + n.z (z - a.z)) / n.x, n = ab x ac, and counts for the voxels with x < x_hit.  An open
+ *   mesh gives what the parity gives.
+ *   DSL_ERR_INVALID (dsl_last_error names the argument), before anything is touched: T = 0 or more than 2^24, a NULL
+ *   vertices / origin / step / dims, both outputs NULL, a dims entry < 1, more than 2^30 voxels, a step entry that is not
+ *   finite and > 0, a non-finite origin, band not > 0 (+inf is allowed: every brick lists every triangle), unknown flags.
+ *   DSL_K_SDF times every launch; DSL_OPT_SDF_* describe the last call.
+ *
+ * dsl_collider_set_volume: a distance volume (dsl_mesh_distance_volume's, or any the host computed) as the collider of the
+ * step.  Exactly one of dev_volume and host_volume is given; the library copies it and owns the copy.  Blocking.
+ * dims = NULL removes the collider.  DSL_ERR_INVALID: a dims entry < 2, more than 2^30 voxels, a bad step or origin as
+ * above, both or neither pointer, unknown flags -- and a mesh collider that is set: a mesh and a volume exclude each other
+ * (dsl_collider_set_mesh refuses likewise while a volume is set; remove the one before setting the other).
+ * DSL_ERR_UNSUPPORTED: a slab handle; and a handle with a volume refuses dsl_slab_config.
+ *   Rule, per fluid particle at x: u_a = (x_a - origin_a) / step_a, i_a = floor(u_a), t_a = u_a - i_a.  No collision when an
+ *   i_a is outside [0, n_a - 2], a corner of the cell is not finite or x is not finite.  With lerp(p, q, t) = p + t (q - p):
+ *   d = the trilinear interpolant of the eight corners, x first, then y, then z; the gradient g_a = (the bilinear
+ *   interpolant of the cell's upper a-face - that of its lower a-face) / step_a, the faces interpolated in axis order
+ *   (x before y before z); |g| = sqrt((g.x g.x + g.y g.y) + g.z g.z).  DSL_SDF_UNSIGNED in flags records that the volume is
+ *   a thin shell; d and g are taken as they are either way.  The particle collides when d < radius and |g| > 0:
+ *   n = g / |g|, x <- x + (radius - d) n and, when v.n < 0, v <- v - ((1 + restitution) (v.n)) n.  Boundary particles,
+ *   the PCISPH predictor state and dsl_stats.max_vel / max_f are not touched.
+ * While a volume is set dsl_collide_pass runs this pass, the step drivers run it where they run the mesh pass (after Update
+ * in dsl_wcsph_step, dsl_pcisph_step and DSL_PCI_END_STEP) and the skin step is not taken.  DSL_OPT_COLLIDE_HITS counts the
+ * particles moved, DSL_K_COLLIDE times the launch.  Without a volume: no launch, no bit changes.
+ * dsl_collider_volume_query: d and n of every fluid particle in host order (zeros where there is no cell, a zero normal
+ * where |g| is not > 0), no response, whatever the radius; either pointer may be NULL.  Blocking.  Not in slab mode. */
+#define DSL_SDF_UNSIGNED 1
+int dsl_mesh_distance_volume(dsl_handle *h, const float *vertices /* 9*T, host */, size_t n_triangles,
+                             const float origin[3], const float step[3], const int32_t dims[3],
+                             float band, int flags, float *dev_out, float *host_out);
+int dsl_collider_set_volume(dsl_handle *h, const float *dev_volume, const float *host_volume, const float origin[3],
+                            const float step[3], const int32_t dims[3], float radius, float restitution, int flags);
+int dsl_collider_volume_query(dsl_handle *h, float *dist /* N */, float *normal /* 3N */);
+
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
 
@@ -785,7 +850,13 @@ enum {
   DSL_OPT_SURFACE_MESH_VCOUNT_MS = 62,     /* (get, blocking) milliseconds of its vertex count launch, as DSL_OPT_SURFACE_COUNT_MS; */
   DSL_OPT_SURFACE_MESH_VSCAN_MS = 63,      /* its vertex scan launches; */
   DSL_OPT_SURFACE_MESH_VEMIT_MS = 64,      /* its vertex emit launch (0 for a call with cap_vertices = 0 or V = 0); */
-  DSL_OPT_SURFACE_MESH_IEMIT_MS = 65       /* its index emit launch (0 for a call with cap_triangles = 0 or without cubes) */
+  DSL_OPT_SURFACE_MESH_IEMIT_MS = 65,      /* its index emit launch (0 for a call with cap_triangles = 0 or without cubes) */
+  /* dsl_mesh_distance_volume, the last call's */
+  DSL_OPT_SDF_ACTIVE_BRICKS = 72,  /* (get, blocking) bricks of 8 x 8 x 4 voxels with a non-empty triangle list */
+  DSL_OPT_SDF_VISITS = 73,         /* (get, blocking) triangle visits: (voxel, triangle) pairs the distance phase tested */
+  DSL_OPT_SDF_DISTANCE_MS = 74,    /* (get, blocking) milliseconds of its distance launch, as DSL_OPT_SURFACE_COUNT_MS; */
+  DSL_OPT_SDF_SIGN_MS = 75,        /* its sign launches: the marks' memset, the sweep, the parity (0 with DSL_SDF_UNSIGNED) */
+  DSL_OPT_COLLIDER_VOLUME = 76     /* (get) voxels of the volume collider; 0: none */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
