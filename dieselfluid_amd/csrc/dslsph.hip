@@ -1468,7 +1468,9 @@ bool skin_usable(const dsl_handle* h) {
 int skin_alloc(dsl_handle* h) {
   int rc = DSL_OK;
   if (!h->skin_state && (rc = dev_alloc(h, &h->skin_state, 1))) return rc;
-  if (!h->lists && (rc = dev_alloc(h, &h->lists, (size_t)kLMaxChunks * h->cap))) return rc;
+  // (kLMaxChunks chunks of 12 bytes per slot, counted in the 16 bytes of the pointer's type)
+  const size_t list_bytes = (size_t)kLMaxChunks * h->cap * sizeof(ListChunk);
+  if (!h->lists && (rc = dev_alloc(h, &h->lists, (list_bytes + sizeof(uint4) - 1) / sizeof(uint4)))) return rc;
   for (int k = 0; k < 6; ++k)
     if (!h->pvz[k] && (rc = dev_alloc(h, &h->pvz[k], (size_t)h->cap))) return rc;
   for (int k = 0; k < 3; ++k)

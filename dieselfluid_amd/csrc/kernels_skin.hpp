@@ -6,11 +6,13 @@
 // Here the expensive part -- counting sort, 216-candidate sweep -- is done once per k steps against the cut-off
 // h (1 + s) on a grid whose cells are h (1 + s) wide, and its result is kept as one LIST per particle:
 //
-//   * an entry is the 16-bit BYTE OFFSET of the neighbour's record in the LDS image of the particle's tile (the tile
-//     tables, the slot order and therefore these offsets stay valid until the next rebuild); eight 16-bit fields make
-//     a 16-byte chunk -- the first field of a particle's first chunk is its entry count -- and chunk c of slot g lives
-//     at lists[c * capacity + g]: one global_load_dwordx4 per lane brings eight neighbours.  While the skin step owns
-//     the grid a tile is 4 x 4 x 3 cells (TileGrid::tbz): with cells h (1 + s) wide that is the ~512 targets and ~1900
+//   * an entry is the 12-bit INDEX of the neighbour's record in the LDS image of the particle's tile (the tile tables,
+//     the slot order and therefore these indices stay valid until the next rebuild; an image holds at most kTCap = 2304
+//     records); eight 12-bit fields make a 12-byte chunk -- field k is bits 12k .. 12k+11 of its 96, the first field of
+//     a particle's first chunk is its entry count -- and chunk c of slot g lives at byte (c * capacity + g) * 12 of the
+//     lists: one global_load_dwordx3 per lane brings eight neighbours, and a shift and an `& 0xfff0` turn a field into
+//     the byte offset ds_read_b128 wants (list_offset).  The kernels take the lists as `uint4*`, a base address.  While
+//     the skin step owns the grid a tile is 4 x 4 x 3 cells (TileGrid::tbz): cells h (1 + s) wide, ~512 targets and ~1900
 //     staged records of the plain step's 4 x 4 x 4 tile, so one 8-wave workgroup walks a tile with every wave busy
 //     and two of them share a CU's LDS, as in the plain step's kernels;
 //   * a list is valid while no particle is further than s h / 2 from the REFERENCE position its list was built at:
@@ -23,7 +25,7 @@
 //     simulation state alone;
 //   * between rebuilds a step is two kernels: k_density_list (sph_field.go:155-172 over the list: 7 VALU
 //     instructions per LISTED pair where the sweep spends 7 per CANDIDATE, 216 of them) and k_force_list (the fused
-//     gradient + viscosity + Update walk: one v_and / v_lshr per pair where the mask walk spends six on bit
+//     gradient + viscosity + Update walk: a shift and a v_and per pair where the mask walk spends six on bit
 //     arithmetic, no per-run set-up, every lane busy until ITS list ends).  A pair beyond h contributes exactly 0
 //     (q = max(1 - r/h, 0)), so the sums are the reference's sums over { |x_i - x_j| < h }.
 //
@@ -36,11 +38,12 @@
 
 namespace dsl {
 
-constexpr int kLEntries = 8;                // 16-bit fields per 16-byte chunk
+constexpr int kLEntries = 8;                // 12-bit fields per 12-byte chunk
 constexpr int kLMaxChunks = 12;             // at most 95 listed neighbours per particle; more: the global-memory sweep
 constexpr int kLMaxEntries = kLMaxChunks * kLEntries - 1;
 constexpr int kLBlock = 512;                // 8 waves, two workgroups per CU (a tile's targets beyond 512 share lanes: for_each_target)
-constexpr unsigned int kLGlobal = 0xffffu;  // count sentinel: this particle takes the global-memory sweep
+constexpr unsigned int kLField = 0xfffu;    // a field's 12 bits
+constexpr unsigned int kLGlobal = 0xfffu;   // count sentinel: this particle takes the global-memory sweep
 constexpr float kSkinTauSteps = 16.0f;      // cap on SkinState::tau, in steps
 constexpr int kLQuads = 14;                 // staging: quads of 4 records per row and pass (36 rows x 14 = 504 lanes)
 static_assert(kTRows * kLQuads <= kLBlock, "one quad per lane");
@@ -56,6 +59,85 @@ constexpr int kListWalk = DSL_LIST_WALK;
 // register cliff by itself; the straight-line walk does only when told: without a viscous term (one 40 KB image: the LDS
 // leaves room for three workgroups per CU) the kernel runs six waves per SIMD at <= 80 VGPRs.
 constexpr int force_list_waves(bool want_v) { return (kListWalk & 2) != 0 && !want_v ? 6 : 4; }
+
+// ---------------------------------------------------------------------------------
+// The chunk: 96 bits in three words, field k in bits 12k .. 12k+11 (fields 2 and 5 straddle two words).  The codec is
+// written with plain shifts so that every compile checks it (the static_asserts below); the compiler makes v_alignbit_b32
+// of funnel().
+// ---------------------------------------------------------------------------------
+static_assert(kTCap <= (int)kLField + 1, "a record index is a 12-bit field");
+static_assert(kLMaxChunks * kLEntries < (int)kLGlobal, "a count is never the sentinel");
+// a chunk in registers
+struct Chunk {
+  unsigned int x, y, z;
+};
+// ... and in memory: 12 bytes, aligned as its words are (global_load_dwordx3 / global_store_dwordx3)
+struct __attribute__((packed, aligned(4))) ListChunk {
+  unsigned int x, y, z;
+};
+static_assert(sizeof(ListChunk) == 12 && alignof(ListChunk) == 4, "chunks lie 12 bytes apart");
+// bits s .. s+31 of hi:lo (0 < s < 32)
+constexpr unsigned int funnel(unsigned int hi, unsigned int lo, int s) { return (lo >> s) | (hi << (32 - s)); }
+// the builders' shift register: after eight pushes the k-th field pushed is field k
+constexpr Chunk chunk_push(const Chunk& b, unsigned int field) {
+  return Chunk{funnel(b.y, b.x, 12), funnel(b.z, b.y, 12), (b.z >> 12) | (field << 20)};
+}
+// field k times 16: the byte offset of record `field k` in a tile's float4 image
+constexpr unsigned int list_offset(const Chunk& e, int k) {
+  switch (k) {
+    case 0: return (e.x << 4) & 0xfff0u;
+    case 1: return (e.x >> 8) & 0xfff0u;
+    case 2: return funnel(e.y, e.x, 20) & 0xfff0u;
+    case 3: return e.y & 0xfff0u;
+    case 4: return (e.y >> 12) & 0xfff0u;
+    case 5: return funnel(e.z, e.y, 24) & 0xfff0u;
+    case 6: return (e.z >> 4) & 0xfff0u;
+    default: return (e.z >> 20) << 4;  // (= (e.z >> 16) & 0xfff0: nothing lies above the last field)
+  }
+}
+// field 0 (a first chunk's count) and the chunk with another value in its place
+constexpr unsigned int list_field0(const Chunk& e) { return e.x & kLField; }
+constexpr Chunk with_field0(const Chunk& e, unsigned int field) { return Chunk{(e.x & ~kLField) | field, e.y, e.z}; }
+// a chunk whose eight fields all hold `field`: four times the 24 bits of a pair
+constexpr Chunk chunk_of(unsigned int field) {
+  const unsigned int u = field | (field << 12);
+  return Chunk{u | (u << 24), (u >> 8) | (u << 16), (u >> 16) | (u << 8)};
+}
+namespace codec_check {
+constexpr Chunk pushed(unsigned int f0, unsigned int f1, unsigned int f2, unsigned int f3, unsigned int f4, unsigned int f5,
+                       unsigned int f6, unsigned int f7) {
+  Chunk b{0xdeadbeefu, 0x01234567u, 0x89abcdefu};  // (what an earlier chunk left in the register is shifted out)
+  const unsigned int f[kLEntries] = {f0, f1, f2, f3, f4, f5, f6, f7};
+  for (int k = 0; k < kLEntries; ++k) b = chunk_push(b, f[k]);
+  return b;
+}
+constexpr bool decodes(const Chunk& e, unsigned int f0, unsigned int f1, unsigned int f2, unsigned int f3, unsigned int f4,
+                       unsigned int f5, unsigned int f6, unsigned int f7) {
+  const unsigned int f[kLEntries] = {f0, f1, f2, f3, f4, f5, f6, f7};
+  for (int k = 0; k < kLEntries; ++k)
+    if (list_offset(e, k) != f[k] << 4) return false;
+  return list_field0(e) == f0;
+}
+constexpr bool same(const Chunk& a, const Chunk& b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
+// one field set at place k, the others clear -- and the complement
+constexpr bool lone(int k, unsigned int v) {
+  unsigned int f[kLEntries] = {}, g[kLEntries] = {};
+  for (int i = 0; i < kLEntries; ++i) f[i] = i == k ? v : 0u, g[i] = i == k ? 0u : kLField;
+  return decodes(pushed(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]), f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]) &&
+         decodes(pushed(g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]);
+}
+static_assert(same(pushed(0, 0, 0, 0, 0, 0, 0, 0), Chunk{0u, 0u, 0u}), "all-zero chunk");
+static_assert(same(pushed(kLField, kLField, kLField, kLField, kLField, kLField, kLField, kLField), Chunk{~0u, ~0u, ~0u}), "all-ones chunk");
+static_assert(decodes(Chunk{0u, 0u, 0u}, 0, 0, 0, 0, 0, 0, 0, 0) && decodes(Chunk{~0u, ~0u, ~0u}, kLField, kLField, kLField, kLField, kLField, kLField, kLField, kLField), "all-zero and all-ones chunks decode");
+static_assert(lone(0, kLField) && lone(1, kLField) && lone(2, kLField) && lone(3, kLField) && lone(4, kLField) &&
+              lone(5, kLField) && lone(6, kLField) && lone(7, kLField), "one field set (or clear) at each of the eight places");
+static_assert(lone(2, 0x801u) && lone(5, 0x801u) && lone(2, 0x7feu) && lone(5, 0x7feu), "the fields that straddle words");
+static_assert(decodes(pushed(0x123, 0x456, 0x789, 0xabc, 0xdef, 0x8ff, 0x900, 0x7a5), 0x123, 0x456, 0x789, 0xabc, 0xdef, 0x8ff, 0x900, 0x7a5), "eight different fields");
+static_assert(same(chunk_of(0x8a5u), pushed(0x8a5, 0x8a5, 0x8a5, 0x8a5, 0x8a5, 0x8a5, 0x8a5, 0x8a5)), "the far-away chunk");
+static_assert(list_field0(with_field0(chunk_of(0x8a5u), 96u)) == 96u && list_offset(with_field0(chunk_of(0x8a5u), 96u), 1) == 0x8a50u &&
+              same(with_field0(with_field0(chunk_of(0x8a5u), 96u), 0x8a5u), chunk_of(0x8a5u)), "the count beside field 1");
+static_assert(list_field0(Chunk{kLGlobal, 0u, 0u}) == kLGlobal && list_field0(with_field0(pushed(0, 1, 2, 3, 4, 5, 6, 7), kLGlobal)) == kLGlobal, "the sentinel");
+}  // namespace codec_check
 
 // first kernel of every skin step: this step's rebuild flag.  The lists are good for the positions the previous step
 // left if no particle is further than s h / 2 from the reference position its list was built at; k_force_list measures
@@ -95,7 +177,13 @@ __global__ void k_skin_decide(SkinState* st) {
 }
 
 // a tile's far-away record (the first pad record of staged row 0), as a list entry
-__device__ __forceinline__ unsigned int pad_entry(const TileMeta& m) { return (unsigned int)(m.row_lds[1] - kTPad) << 4; }
+__device__ __forceinline__ unsigned int pad_entry(const TileMeta& m) { return (unsigned int)(m.row_lds[1] - kTPad); }
+// the lists as the chunks they are (the kernels take them as `uint4*`: a base address)
+__device__ __forceinline__ ListChunk* list_chunks(uint4* lists) { return reinterpret_cast<ListChunk*>(lists); }
+__device__ __forceinline__ const ListChunk* list_chunks(const uint4* lists) { return reinterpret_cast<const ListChunk*>(lists); }
+__device__ __forceinline__ void store_chunk(uint4* __restrict__ lists, size_t index, const Chunk& e) {
+  list_chunks(lists)[index] = ListChunk{e.x, e.y, e.z};
+}
 
 // ---------------------------------------------------------------------------------
 // masks of the wide candidate sweep (k_density_pair<.., WIDE>) -> lists.  One lane per target; the tile's table says
@@ -116,11 +204,11 @@ __global__ __launch_bounds__(kLBlock) void k_list_build_v1(DevConsts c, TileGrid
   if (gate.closed()) return;
   __shared__ TileMeta metas[2];
   // A lane finishes its chunks at its own pace (the bit loops below diverge), and a chunk stored the moment it was full
-  // went out as a lone 16-byte write: 1.6 GB of them per 16M rebuild, 1.7 ms.  The first kLStaged chunks of a list
+  // went out as a lone chunk-sized write: 1.6 GB of them per 16M rebuild, 1.7 ms.  The first kLStaged chunks of a list
   // therefore wait in LDS (a lane reads back only what it wrote itself: no barrier) and leave together at the end of the
-  // pass, 1 KB per wave and store.  Longer lists (more than 63 entries: rare) store the rest directly.
+  // pass, 768 bytes per wave and store.  Longer lists (more than 63 entries: rare) store the rest directly.
   constexpr int kLStaged = 8;
-  __shared__ uint4 held[kLStaged][kLBlock];
+  __shared__ ListChunk held[kLStaged][kLBlock];
   __shared__ unsigned int tile_fields[2];
   const int tid = threadIdx.x;
   if (tid < 2) tile_fields[tid] = 0u;
@@ -142,24 +230,21 @@ __global__ __launch_bounds__(kLBlock) void k_list_build_v1(DevConsts c, TileGrid
       if (SHARED && sub != 0) return;  // (a short pass's list is built by the first lane of its group)
       const TileTarget tt = tile_target(m, t);
       const int g = tt.g;
-      // a 128-bit shift register: the k-th field pushed into a chunk ends up in bits 16k .. 16k+15.  Field 0 of chunk 0
-      // is the length, patched in at the end.
-      unsigned int b0 = 0u, b1 = 0u, b2 = 0u, b3 = 0u;
+      // a 96-bit shift register (chunk_push): the k-th field pushed into a chunk ends up in bits 12k .. 12k+11.  Field 0
+      // of chunk 0 is the length, patched in at the end.
+      Chunk b{0u, 0u, 0u};
       int n = 0;  // fields pushed, the length's included
       auto push = [&](unsigned int entry) {
-        b0 = __builtin_amdgcn_alignbit(b1, b0, 16);
-        b1 = __builtin_amdgcn_alignbit(b2, b1, 16);
-        b2 = __builtin_amdgcn_alignbit(b3, b2, 16);
-        b3 = (b3 >> 16) | (entry << 16);
+        b = chunk_push(b, entry);
         n += 1;
         if ((n & (kLEntries - 1)) == 0) {
           const int ch = (n >> 3) - 1;
-          if (ch < kLStaged) held[ch][tid] = make_uint4(b0, b1, b2, b3);
-          else if (ch < kLMaxChunks) lists[(size_t)ch * lstride + g] = make_uint4(b0, b1, b2, b3);
+          if (ch < kLStaged) held[ch][tid] = ListChunk{b.x, b.y, b.z};
+          else if (ch < kLMaxChunks) store_chunk(lists, (size_t)ch * lstride + g, b);
         }
       };
       auto emit = [&](int rec) {
-        if (rec != tt.own) push((unsigned int)rec << 4);  // (the particle itself is no entry: sph_field.go:164)
+        if (rec != tt.own) push((unsigned int)rec);  // (the particle itself is no entry: sph_field.go:164)
       };
       const bool masks = m.overflow == 0;  // (a tile beyond the LDS budget was not swept: the global-memory sweep)
       if (masks) {
@@ -227,11 +312,12 @@ __global__ __launch_bounds__(kLBlock) void k_list_build_v1(DevConsts c, TileGrid
         while (n < nch * kLEntries) push(pad);  // the far-away record up to the end of the wave's last chunk
       // the held chunks leave together; field 0 of the first one is the length (or the mark of an unlisted target)
       for (int ch = 0; ch < min(nch, kLStaged); ++ch) {
-        uint4 v = held[ch][tid];
-        if (ch == 0) v.x = (v.x & 0xffff0000u) | (unsigned int)fields;
-        if (fits) lists[(size_t)ch * lstride + g] = v;
+        const ListChunk hv = held[ch][tid];
+        Chunk v{hv.x, hv.y, hv.z};
+        if (ch == 0) v = with_field0(v, (unsigned int)fields);
+        if (fits) store_chunk(lists, (size_t)ch * lstride + g, v);
       }
-      if (!fits) lists[g] = make_uint4(kLGlobal, 0u, 0u, 0u);
+      if (!fits) store_chunk(lists, g, Chunk{kLGlobal, 0u, 0u});
     });
     if (have) tile_meta_store(metas[cur ^ 1], table_word);
     sync_lds();
@@ -369,8 +455,8 @@ __global__ __launch_bounds__(kLBlock, 4) void k_list_build(DevConsts c, TileGrid
       const int nch = (fields + kLEntries - 1) / kLEntries;       // this lane's chunks (full pass: the wave's)
       const int nch_wave = (wmax + kLEntries - 1) / kLEntries;    // the loop's
       // ---- one field per trip and lane
-      unsigned int b0 = 0u, b1 = 0u, b2 = 0u, b3 = 0u;            // a 128-bit shift register: field k of a chunk ends up in bits 16k .. 16k+15
-      unsigned int k0 = 0u, k1 = 0u, k2 = 0u, k3 = 0u;            // chunk 0, kept for its length field
+      Chunk b{0u, 0u, 0u};                                        // a 96-bit shift register (chunk_push): field k of a chunk ends up in bits 12k .. 12k+11
+      Chunk first{0u, 0u, 0u};                                    // chunk 0, kept for its length field
       int qi = 0;
       unsigned int w = 0u, top = 0u;
       // (the next item is fetched one trip before it is needed)
@@ -393,25 +479,21 @@ __global__ __launch_bounds__(kLBlock, 4) void k_list_build(DevConsts c, TileGrid
           if (w != 0u) {
             const int b = __builtin_ctz(w);
             w &= w - 1u;
-            entry = (top - (unsigned int)b) << 4;
+            entry = top - (unsigned int)b;
           }
         }
-        b0 = __builtin_amdgcn_alignbit(b1, b0, 16);
-        b1 = __builtin_amdgcn_alignbit(b2, b1, 16);
-        b2 = __builtin_amdgcn_alignbit(b3, b2, 16);
-        b3 = (b3 >> 16) | (entry << 16);
+        b = chunk_push(b, entry);
         if ((it & (kLEntries - 1)) == kLEntries - 1) {
           const int ch = it >> 3;
           if (ch == 0) {
-            k0 = b0, k1 = b1, k2 = b2, k3 = b3;
+            first = b;
           } else if (ch < nch) {
-            lists[(size_t)ch * lstride + g] = make_uint4(b0, b1, b2, b3);
+            store_chunk(lists, (size_t)ch * lstride + g, b);
           }
         }
       }
       // field 0 of the first chunk is the length (or the mark of an unlisted target)
-      if (fits) lists[g] = make_uint4((k0 & 0xffff0000u) | (unsigned int)fields, k1, k2, k3);
-      else lists[g] = make_uint4(kLGlobal, 0u, 0u, 0u);
+      store_chunk(lists, g, fits ? with_field0(first, (unsigned int)fields) : Chunk{kLGlobal, 0u, 0u});
     });
     if (have) tile_meta_store(metas[cur ^ 1], table_word);
     sync_lds();
@@ -475,23 +557,20 @@ __device__ __forceinline__ const float4& lds_at(const float4* base, unsigned int
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_offset);
 }
 
-// a chunk in registers (plain words: HIP's uint4 goes through memory when a member is rewritten)
-struct Chunk {
-  unsigned int x, y, z, w;
-};
+// a chunk into registers (Chunk's plain words: HIP's vector types go through memory when a member is rewritten)
+__device__ __forceinline__ Chunk load_chunk(const ListChunk* __restrict__ chunks, size_t index) {
+  const ListChunk v = chunks[index];
+  return Chunk{v.x, v.y, v.z};
+}
 __device__ __forceinline__ Chunk load_chunk(const uint4* __restrict__ lists, size_t index) {
-  const uint4 v = lists[index];
-  return Chunk{v.x, v.y, v.z, v.w};
+  return load_chunk(list_chunks(lists), index);
 }
 // a chunk whose eight fields all name the tile's far-away record
-__device__ __forceinline__ Chunk pad_chunk(unsigned int pad) {
-  const unsigned int w = pad | (pad << 16);
-  return Chunk{w, w, w, w};
-}
+__device__ __forceinline__ Chunk pad_chunk(unsigned int pad) { return chunk_of(pad); }
 // a particle's first chunk: the count out of field 0, the far-away record in its place
 __device__ __forceinline__ unsigned int take_count(Chunk& e, unsigned int pad) {
-  const unsigned int cnt = e.x & 0xffffu;
-  e.x = (e.x & 0xffff0000u) | pad;
+  const unsigned int cnt = list_field0(e);
+  e = with_field0(e, pad);
   return cnt;
 }
 // Loads that only ONE successor of a branch uses are moved into that successor by the compiler: the records an exit of
@@ -503,14 +582,13 @@ __device__ __forceinline__ void loads_issued() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
-typedef unsigned int ListWords __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) ListWords* ListPtr;  // (global memory by type: nothing left to infer)
-__device__ __forceinline__ unsigned long long unknown_pointer(const uint4* p) {
+typedef const __attribute__((address_space(1))) ListChunk* ListPtr;  // (global memory by type: nothing left to infer)
+__device__ __forceinline__ unsigned long long unknown_pointer(const ListChunk* p) {
   unsigned long long a = reinterpret_cast<unsigned long long>(p);
   asm volatile("" : "+v"(a));
   return a;
 }
-__device__ __forceinline__ unsigned long long unknown_pointer_uniform(const uint4* p) {
+__device__ __forceinline__ unsigned long long unknown_pointer_uniform(const ListChunk* p) {
   unsigned long long a = reinterpret_cast<unsigned long long>(p);
   asm volatile("" : "+s"(a));
   return a;
@@ -519,7 +597,7 @@ __device__ __forceinline__ unsigned long long unknown_pointer_uniform(const uint
 // chunks each, a scalar).  Chunk ch lives in c[ch % 3]; request(ch), at the head of chunk ch, loads chunk ch + 2 into the
 // place chunk ch - 1 has left.  The load is UNCONDITIONAL, so that the compiler counts the loads in flight (s_waitcnt
 // vmcnt(1)) where a branch around the load made it wait for all of them.  Past the list's end every lane asks for the
-// same 16 bytes, the last chunk of the wave's first list: one 64-byte line that the wave has asked for before, with
+// same 12 bytes, the last chunk of the wave's first list: a 64-byte line or two that the wave has asked for before, with
 // entries of this tile in it (a walk requests -- and never reads -- the records of a word or two behind its list's end).
 // `ch` is a constant of the unrolled walk: every chunk has registers of its own and nothing is copied from one place
 // to another.
@@ -530,17 +608,17 @@ struct ChunkRing {
   int lstride, nch;
   __device__ __forceinline__ ChunkRing(const uint4* __restrict__ lists, int lstride_, int g, int nch_, const Chunk& q0,
                                        const Chunk& q1)
-      : next(unknown_pointer(lists + (size_t)2 * lstride_ + g)),
-        last(unknown_pointer_uniform(lists + (size_t)max(nch_ - 1, 0) * lstride_ + __builtin_amdgcn_readfirstlane(g))),
+      : next(unknown_pointer(list_chunks(lists) + (size_t)2 * lstride_ + g)),
+        last(unknown_pointer_uniform(list_chunks(lists) + (size_t)max(nch_ - 1, 0) * lstride_ + __builtin_amdgcn_readfirstlane(g))),
         lstride(lstride_), nch(nch_) {
     c[0] = q0;
     c[1] = q1;
   }
   __device__ __forceinline__ void request(int ch) {
     if (ch + 2 >= kLMaxChunks) return;
-    const ListWords v = *(ListPtr)(ch + 2 < nch ? next : last);
-    c[(ch + 2) % 3] = Chunk{v.x, v.y, v.z, v.w};
-    next += (unsigned long long)lstride * sizeof(uint4);
+    const ListPtr v = (ListPtr)(ch + 2 < nch ? next : last);
+    c[(ch + 2) % 3] = Chunk{v->x, v->y, v->z};  // (adjacent words: one global_load_dwordx3)
+    next += (unsigned long long)lstride * sizeof(ListChunk);
   }
   __device__ __forceinline__ const Chunk& at(int ch) const { return c[ch % 3]; }
 };
@@ -563,14 +641,14 @@ __device__ __forceinline__ void walk_shared(const uint4* __restrict__ lists, int
   for (int ch = sub; __builtin_amdgcn_ballot_w64(ch < nch) != 0ull; ch += k) {
     Chunk e = pad_chunk(pad);
     if (ch < nch) e = load_chunk(lists, (size_t)ch * lstride + g);
-    if (ch == 0) e.x = (e.x & 0xffff0000u) | pad;  // (the length's field)
+    if (ch == 0) e = with_field0(e, pad);  // (the length's field)
     body(e);
   }
 }
 // field 0 of slot g's first chunk, as the group's lane 0 reads it
 __device__ __forceinline__ unsigned int shared_fields(const uint4* __restrict__ lists, int g, int sub) {
   unsigned int f = 0u;
-  if (sub == 0) f = lists[g].x & 0xffffu;
+  if (sub == 0) f = list_chunks(lists)[g].x & kLField;
   return (unsigned int)__shfl((int)f, (int)((threadIdx.x & (kWave - 1)) - sub), kWave);
 }
 
@@ -580,7 +658,9 @@ __device__ __forceinline__ unsigned int shared_fields(const uint4* __restrict__ 
 // ---------------------------------------------------------------------------------
 // (walks its share of the tile list the static way: the tile queue's one register more -- thread 0's pending draw -- costs
 // this HBM-bound kernel its sixth wave per SIMD, 0.43 -> 0.55 ms; the force walk gains 5 % from the queue)
-__global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGrid tg, const int* __restrict__ desc_of,
+// (six waves per SIMD are asked for: left to itself the compiler takes 83 VGPRs with the 12-bit decode -- two more in the
+// later passes' copy of the walk and one that holds scalar registers, the decode's constants among them)
+__global__ __launch_bounds__(kLBlock, 6) void k_density_list(DevConsts c, TileGrid tg, const int* __restrict__ desc_of,
                                                              const int* __restrict__ n_tiles, const int* __restrict__ desc,
                                                              const int* __restrict__ cell_start, const SkinState* st,
                                                              CSoa3 pX, CSoa3 pZ, const uint4* __restrict__ lists,
@@ -645,11 +725,11 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
         const float sx = two_hh * me.x, sy = two_hh * me.y, sz = two_hh * me.z, a0 = 1.0f + me.w;
         float acc0 = 0.0f, acc1 = 0.0f;
         float4 cq[4];
-        auto fetch4 = [&](unsigned int w0, unsigned int w1) {
-          cq[0] = lds_at(A, w0 & 0xffffu);
-          cq[1] = lds_at(A, w0 >> 16);
-          cq[2] = lds_at(A, w1 & 0xffffu);
-          cq[3] = lds_at(A, w1 >> 16);
+        // the records of a chunk's first (fields 0-3: bits 0-47) or second half (fields 4-7: bits 48-95)
+        // (`half` is a constant at every call: list_offset's switch folds)
+        auto fetch4 = [&](const Chunk& e, int half) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) cq[u] = lds_at(A, list_offset(e, 4 * half + u));
         };
         auto sum4 = [&](const float4 (&r)[4]) {
 #pragma unroll
@@ -661,9 +741,9 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
         };
         if constexpr (SHARED) {
           walk_shared(lists, lstride, g, pad, sub, k, fields, [&](const Chunk& e) {
-            fetch4(e.x, e.y);
+            fetch4(e, 0);
             float4 c1[4] = {cq[0], cq[1], cq[2], cq[3]};
-            fetch4(e.z, e.w);
+            fetch4(e, 1);
             sum4(c1);
             sum4(cq);
           });
@@ -674,19 +754,19 @@ __global__ __launch_bounds__(kLBlock, 4) void k_density_list(DevConsts c, TileGr
           // waited for in the trip that requests it.  Straight-line code as in k_force_list keeps two chunks in flight
           // and is no faster, 0.404 -> 0.407 ms: profiles/HISTORY.md, "List walks: straight-line code over the chunks".)
           const int nf = __builtin_amdgcn_readfirstlane((int)fields), nch = (nf + kLEntries - 1) >> 3;
-          const uint4* lp = lists + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
+          const ListChunk* lp = list_chunks(lists) + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
           Chunk e = q0, e1 = q1;
-          fetch4(e.x, e.y);
+          fetch4(e, 0);
           for (int ch = 0;;) {
             float4 c1[4] = {cq[0], cq[1], cq[2], cq[3]};
-            fetch4(e.z, e.w);  // the chunk's second half
+            fetch4(e, 1);  // the chunk's second half
             sum4(c1);
             if (8 * ch + 4 >= nf) break;  // (the half just requested is never read: four reads more)
             const Chunk en = e1;
             if (ch + 2 < nch) e1 = load_chunk(lp, 0);
             lp += lstride;
             float4 c2[4] = {cq[0], cq[1], cq[2], cq[3]};
-            fetch4(en.x, en.y);
+            fetch4(en, 0);
             sum4(c2);
             e = en;
             ch += 1;
@@ -864,28 +944,28 @@ __global__ __launch_bounds__(kLBlock, force_list_waves(WANT_V)) void k_force_lis
           };
           if constexpr (SHARED) {
             walk_shared(lists, lstride, g, pad, sub, k, fields, [&](const Chunk& e) {
-              const unsigned int w[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
               for (int u = 0; u < 4; ++u) {
-                const Pair1 r0 = fetch1(w[u] & 0xffffu), r1 = fetch1(w[u] >> 16);
+                const Pair1 r0 = fetch1(list_offset(e, 2 * u)), r1 = fetch1(list_offset(e, 2 * u + 1));
                 accum(r0.a, r0.b);
                 accum(r1.a, r1.b);
               }
             });
           } else {
-            // The wave's lists have one length (k_list_build): a scalar walk over the 32-bit words of the chunks.  p0, p1
-            // hold the records of the word being walked, every step consumes one and requests the field two ahead, so
-            // four reads are in flight while a pair's ~25 VALU instructions issue.
+            // The wave's lists have one length (k_list_build): a scalar walk over the chunks' pairs of fields ("words":
+            // word u of a chunk is its fields 2u and 2u + 1, a constant at every call).  p0, p1 hold the records of the
+            // word being walked, every step consumes one and requests the field two ahead, so four reads are in flight
+            // while a pair's ~25 VALU instructions issue.
             constexpr bool kStraight = (kListWalk & 2) != 0;
             const int nf = __builtin_amdgcn_readfirstlane((int)fields), nch = (nf + kLEntries - 1) >> 3;
-            Pair1 p0 = fetch1(q0.x & 0xffffu), p1 = fetch1(q0.x >> 16);
-            auto word = [&](unsigned int next_word) {
+            Pair1 p0 = fetch1(list_offset(q0, 0)), p1 = fetch1(list_offset(q0, 1));
+            auto word = [&](const Chunk& next, int u) {
               Pair1 cu = p0;
-              p0 = fetch1(next_word & 0xffffu);
+              p0 = fetch1(list_offset(next, 2 * u));
               if constexpr (kStraight) loads_issued();
               accum(cu.a, cu.b);
               cu = p1;
-              p1 = fetch1(next_word >> 16);
+              p1 = fetch1(list_offset(next, 2 * u + 1));
               if constexpr (kStraight) loads_issued();
               accum(cu.a, cu.b);
             };
@@ -900,34 +980,34 @@ __global__ __launch_bounds__(kLBlock, force_list_waves(WANT_V)) void k_force_lis
               for (int ch = 0; ch < kLMaxChunks; ++ch) {
                 ring.request(ch);
                 const Chunk& e = ring.at(ch);
-                word(e.y);
+                word(e, 1);
                 if (8 * ch + 2 >= nf) break;  // (the word just requested is never read: four reads more)
-                word(e.z);
+                word(e, 2);
                 if (8 * ch + 4 >= nf) break;
-                word(e.w);
+                word(e, 3);
                 if (8 * ch + 6 >= nf) break;
                 if (ch + 1 == kLMaxChunks) {  // (no chunk behind the last: its fourth word ends the walk)
                   accum(p0.a, p0.b);
                   accum(p1.a, p1.b);
                   break;
                 }
-                word(ring.at(ch + 1).x);
+                word(ring.at(ch + 1), 0);
                 if (8 * ch + 8 >= nf) break;
               }
             } else {
-              const uint4* lp = lists + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
+              const ListChunk* lp = list_chunks(lists) + (size_t)2 * lstride + g;  // chunk ch + 2 of this slot
               Chunk e = q0, e1 = q1;
               for (int ch = 0;;) {
-                word(e.y);
+                word(e, 1);
                 if (8 * ch + 2 >= nf) break;  // (the word just requested is never read: four reads more)
-                word(e.z);
+                word(e, 2);
                 if (8 * ch + 4 >= nf) break;
-                word(e.w);
+                word(e, 3);
                 if (8 * ch + 6 >= nf) break;
                 const Chunk en = e1;
                 if (ch + 2 < nch) e1 = load_chunk(lp, 0);
                 lp += lstride;
-                word(en.x);
+                word(en, 0);
                 e = en;
                 ch += 1;
                 if (8 * ch >= nf) break;
