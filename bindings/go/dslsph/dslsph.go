@@ -980,3 +980,46 @@ func (e *Engine) ColliderVolumeQuery() (dist, normal []float32, err error) {
 	err = e.ck(C.dsl_collider_volume_query(e.h, (*C.float)(unsafe.Pointer(&dist[0])), (*C.float)(unsafe.Pointer(&normal[0]))))
 	return
 }
+
+// ---- the volume collider in rigid motion (include/dslsph.h: dsl_collider_volume_motion) ----
+
+// 1 while a motion is set (dsl_get_option)
+const OptColliderVolumeMoving = int(C.DSL_OPT_COLLIDER_VOLUME_MOVING)
+
+// ColliderMotion: the rigid motion of the volume collider -- the reference's Collider.Origin / UpdateOrigin
+// (render/mesh/collider.go:10-36) with an orientation and the body's velocities.  Rot: row-major R, its columns the body's
+// axes in world coordinates; Trans: the body frame's origin; LinVel: the body's velocity there; AngVel: its angular
+// velocity; all in world coordinates.
+type ColliderMotion struct {
+	Rot    [9]float32
+	Trans  [3]float32
+	LinVel [3]float32
+	AngVel [3]float32
+}
+
+// IdentityMotion: the body where it was built, at rest
+func IdentityMotion() ColliderMotion {
+	return ColliderMotion{Rot: [9]float32{1, 0, 0, 0, 1, 0, 0, 0, 1}}
+}
+
+// SetColliderVolumeMotion: the pose and velocities every later collide pass uses; the voxels are not touched, nothing is
+// synchronised.  The library does not integrate the pose: a host that moves a body calls this between single steps.
+func (e *Engine) SetColliderVolumeMotion(m ColliderMotion) error {
+	return e.ck(C.dsl_collider_volume_motion(e.h, (*C.float)(unsafe.Pointer(&m.Rot[0])), (*C.float)(unsafe.Pointer(&m.Trans[0])), (*C.float)(unsafe.Pointer(&m.LinVel[0])), (*C.float)(unsafe.Pointer(&m.AngVel[0]))))
+}
+
+// ClearColliderVolumeMotion: motion off (Collider.IsStatic again): the static pass runs
+func (e *Engine) ClearColliderVolumeMotion() error {
+	return e.ck(C.dsl_collider_volume_motion(e.h, nil, nil, nil, nil))
+}
+
+// ColliderVolumeImpulse: what the fluid handed to the body since the last reset -- the impulse and the torque impulse about
+// Trans (blocking); reset zeroes the accumulators after the read.
+func (e *Engine) ColliderVolumeImpulse(reset bool) (impulse, torque [3]float32, err error) {
+	r := 0
+	if reset {
+		r = 1
+	}
+	err = e.ck(C.dsl_collider_volume_impulse(e.h, (*C.float)(unsafe.Pointer(&impulse[0])), (*C.float)(unsafe.Pointer(&torque[0])), C.int(r)))
+	return
+}

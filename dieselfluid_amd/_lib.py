@@ -119,6 +119,8 @@ EXPORTS = {
     "dsl_mesh_distance_volume": (C.c_int, [_vp, _fp, C.c_size_t, _fp, _fp, _ip, C.c_float, C.c_int, _vp, _fp]),
     "dsl_collider_set_volume": (C.c_int, [_vp, _vp, _fp, _fp, _fp, _ip, C.c_float, C.c_float, C.c_int]),
     "dsl_collider_volume_query": (C.c_int, [_vp, _fp, _fp]),
+    "dsl_collider_volume_motion": (C.c_int, [_vp, _fp, _fp, _fp, _fp]),
+    "dsl_collider_volume_impulse": (C.c_int, [_vp, _fp, _fp, C.c_int]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

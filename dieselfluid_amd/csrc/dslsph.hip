@@ -1807,7 +1807,8 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_SDF_VISITS:
     case DSL_OPT_SDF_DISTANCE_MS:
     case DSL_OPT_SDF_SIGN_MS:
-    case DSL_OPT_COLLIDER_VOLUME: return sdf_option(h, option, value);  // (blocking but the last)
+    case DSL_OPT_COLLIDER_VOLUME:
+    case DSL_OPT_COLLIDER_VOLUME_MOVING: return sdf_option(h, option, value);  // (blocking but the last)
     default: return fail(h, DSL_ERR_INVALID, "dsl_get_option: unknown option");
   }
 }

@@ -9,6 +9,7 @@
 //   surface.hip        fluid surfaces: dsl_surface_extract, dsl_field_surface and their four kernels (likewise)
 //   surface_mesh.hip   the indexed mesh: dsl_surface_extract_indexed, dsl_field_surface_indexed and their three kernels
 //   sdf.hip            implicit colliders: dsl_mesh_distance_volume, dsl_collider_set_volume, the volume collide pass, their kernels
+//   sdf_rigid.hip      the volume collider in rigid motion: dsl_collider_volume_motion, dsl_collider_volume_impulse, their two kernels
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -237,6 +238,15 @@ struct dsl_handle {
   float colv_radius = 0.0f, colv_rest = 0.0f;
   int colv_flags = 0;
   float* colv_query = nullptr;
+  // ... in rigid motion (sdf_rigid.hip; dsl_collider_volume_motion).  colv_moving: a motion is set -- the collide pass and the
+  // query run k_collide_volume_rigid with these 18 numbers by value; colv_partial: six sums per workgroup of the last pass,
+  // component-major; colv_acc: impulse and torque impulse since the last reset.  Both allocated when a motion is first set
+  bool colv_moving = false;
+  float colv_rot[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+  float colv_trans[3] = {}, colv_lin[3] = {}, colv_ang[3] = {};
+  float* colv_partial = nullptr;
+  size_t colv_partial_count = 0;
+  float* colv_acc = nullptr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -400,5 +410,11 @@ void surface_mesh_free(dsl_handle* h);
 int sdf_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SDF_* and DSL_OPT_COLLIDER_VOLUME (get)
 void sdf_free(dsl_handle* h);
 int collide_volume_pass(dsl_handle* h);  // the collide pass while a volume collider is set
+
+// ---- defined in sdf_rigid.hip ----
+void sdf_rigid_free(dsl_handle* h);
+int collide_volume_rigid_reset(dsl_handle* h);  // motion off, the accumulators at zero (dsl_collider_set_volume)
+int collide_volume_rigid_pass(dsl_handle* h);   // the collide pass while a motion is set: the rigid pass and the fold
+int collide_volume_rigid_query(dsl_handle* h, float* qd, float* qn);  // dsl_collider_volume_query's launch at the pose in force
 
 }  // namespace dsl

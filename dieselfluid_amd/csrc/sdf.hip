@@ -1,7 +1,8 @@
 // sdf.hip -- implicit colliders: the signed distance volume of a triangle mesh on a voxel lattice (dsl_mesh_distance_volume)
 // and the collision of the fluid particles with such a volume inside the step (dsl_collider_set_volume, the volume branch of
 // dsl_collide_pass, dsl_collider_volume_query).  A translation unit of its own with its kernels and their host side; its
-// kernel list is tests/golden/device_kernels_sdf.txt.  Same flags as dslsph.hip: -ffp-contract=off keeps every operation at
+// kernel list is tests/golden/device_kernels_sdf.txt (the collider in rigid motion is sdf_rigid.hip, reached from the
+// dispatches below).  Same flags as dslsph.hip: -ffp-contract=off keeps every operation at
 // one rounding, `/` and sqrtf are the correctly rounded ones.  Both rules are build-defined (include/dslsph.h)
 // and restated operation for operation in tests/sdf_ref.py; they are the same in DSL_MATH_EXACT and DSL_MATH_FAST.
 //
@@ -48,6 +49,7 @@ struct ColVol {
 };
 
 namespace {
+// (sdf_rigid.hip keeps copies of sdf_sync_lds, sdf_dot and k_collide_volume's cell evaluation: a change to one belongs in both)
 __device__ __forceinline__ void sdf_sync_lds() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
@@ -410,6 +412,10 @@ int sdf_option(dsl_handle* h, int option, double* value) {
     *value = h->colv_on ? (double)h->colv_n[0] * h->colv_n[1] * h->colv_n[2] : 0.0;
     return DSL_OK;
   }
+  if (option == DSL_OPT_COLLIDER_VOLUME_MOVING) {
+    *value = h->colv_moving ? 1.0 : 0.0;
+    return DSL_OK;
+  }
   if (option == DSL_OPT_SDF_ACTIVE_BRICKS || option == DSL_OPT_SDF_VISITS) {
     unsigned long long ctr[kSdfCounters] = {};
     if (h->sdf_ctr) {
@@ -440,12 +446,14 @@ void sdf_free(dsl_handle* h) {
   (void)hipFree(h->sdf_marks);
   (void)hipFree(h->colv_vol);
   (void)hipFree(h->colv_query);
+  sdf_rigid_free(h);
   for (hipEvent_t e : h->sdf_ev)
     if (e) (void)hipEventDestroy(e);
 }
 
 // The volume branch of the collide pass: in place on the current state.  dsl_stats.max_vel / max_f stay what Update saw.
 int collide_volume_pass(dsl_handle* h) {
+  if (h->colv_moving) return collide_volume_rigid_pass(h);  // (sdf_rigid.hip)
   HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
   const int rc = timed(h, DSL_K_COLLIDE, [&] {
     hipLaunchKernelGGL(k_collide_volume<true>, dim3((unsigned)((h->n + kSdfBlock - 1) / kSdfBlock)), dim3(kSdfBlock), 0, h->stream,
@@ -569,7 +577,7 @@ int dsl_collider_set_volume(dsl_handle* h, const float* dev_volume, const float*
   if (!dims) {  // removes the collider (the copy stays for the next one)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->colv_on = false;
-    return DSL_OK;
+    return collide_volume_rigid_reset(h);
   }
   if (h->col_tri > 0)
     return fail(h, DSL_ERR_INVALID, w + ": a mesh collider is set, and a mesh collider and a volume collider exclude each other; "
@@ -587,6 +595,7 @@ int dsl_collider_set_volume(dsl_handle* h, const float* dev_volume, const float*
   if (flags & ~DSL_SDF_UNSIGNED) return fail(h, DSL_ERR_INVALID, w + ": unknown bits in flags");
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the volume that is replaced)
   h->colv_on = false;  // no collider until the new one is whole
+  if (int rc = collide_volume_rigid_reset(h)) return rc;  // ... and a new volume starts at rest, with nothing handed over
   if (int rc = surf_reserve(h, &h->colv_vol, &h->colv_count, (size_t)nvox, "dsl_collider_set_volume: the volume")) return rc;
   if (!h->col_hits)
     if (int rc = dev_alloc(h, &h->col_hits, 1)) return rc;
@@ -615,10 +624,14 @@ int dsl_collider_volume_query(dsl_handle* h, float* dist, float* normal) {
     if (int rc = dev_alloc(h, &h->colv_query, (size_t)4 * h->cap)) return rc;
   float* qd = h->colv_query;
   float* qn = h->colv_query + nf;
-  hipLaunchKernelGGL(k_collide_volume<false>, dim3((unsigned)((h->n + kSdfBlock - 1) / kSdfBlock)), dim3(kSdfBlock), 0, h->stream, h->n,
-                     bnd_of(h), col_vol(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), dist ? qd : nullptr, normal ? qn : nullptr,
-                     (const int*)h->ids[h->cur_ids], (int*)nullptr);
-  HIP_TRY(h, hipGetLastError());
+  if (h->colv_moving) {
+    if (int rc = collide_volume_rigid_query(h, dist ? qd : nullptr, normal ? qn : nullptr)) return rc;
+  } else {
+    hipLaunchKernelGGL(k_collide_volume<false>, dim3((unsigned)((h->n + kSdfBlock - 1) / kSdfBlock)), dim3(kSdfBlock), 0, h->stream, h->n,
+                       bnd_of(h), col_vol(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), dist ? qd : nullptr, normal ? qn : nullptr,
+                       (const int*)h->ids[h->cur_ids], (int*)nullptr);
+    HIP_TRY(h, hipGetLastError());
+  }
   if (dist) HIP_TRY(h, hipMemcpyAsync(dist, qd, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   if (normal) HIP_TRY(h, hipMemcpyAsync(normal, qn, 3 * nf * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -539,6 +539,33 @@ class SPHEngine:
         self._ck(self._L.dsl_collider_volume_query(self._h, _fp(dist), _fp(nrm)))
         return dist, nrm
 
+    def set_collider_volume_motion(self, rot=None, trans=None, lin_vel=None, ang_vel=None):
+        """The volume collider as a rigid body in motion (dsl_collider_volume_motion): `rot` (3, 3) row-major, its columns the
+        body's axes in world coordinates; `trans` the body frame's origin; `lin_vel` the body's velocity there and `ang_vel` its
+        angular velocity, world.  None is the identity / zero; all four None turn motion off.  The voxels are not touched; the
+        pose holds until the next call (the library does not integrate it)."""
+        def arr(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if a.size != n:
+                raise DslError(f"set_collider_volume_motion: {what} takes {n} values")
+            return a
+        r, t, lv, av = arr(rot, 9, "rot"), arr(trans, 3, "trans"), arr(lin_vel, 3, "lin_vel"), arr(ang_vel, 3, "ang_vel")
+        ptr = lambda a: _fp(a) if a is not None else None
+        self._ck(self._L.dsl_collider_volume_motion(self._h, ptr(r), ptr(t), ptr(lv), ptr(av)))
+
+    def clear_collider_volume_motion(self):
+        """motion off: the static pass runs again (the accumulated impulse stays until it is read and reset)"""
+        self._ck(self._L.dsl_collider_volume_motion(self._h, None, None, None, None))
+
+    def collider_volume_impulse(self, reset: bool = False):
+        """(impulse (3,), torque impulse about `trans` (3,)): what the fluid handed to the moving body since the last reset"""
+        imp = np.zeros(3, dtype=np.float32)
+        trq = np.zeros(3, dtype=np.float32)
+        self._ck(self._L.dsl_collider_volume_impulse(self._h, _fp(imp), _fp(trq), 1 if reset else 0))
+        return imp, trq
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -694,7 +721,8 @@ class SPHEngine:
                "surface_triangles": 56, "surface_active_bricks": 57, "surface_count_ms": 58, "surface_scan_ms": 59,
                "surface_emit_ms": 60, "surface_vertices": 61, "surface_mesh_vcount_ms": 62, "surface_mesh_vscan_ms": 63,
                "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65,
-               "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76}
+               "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76,
+               "collider_volume_moving": 77}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

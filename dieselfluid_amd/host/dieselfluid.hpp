@@ -278,6 +278,7 @@ class SPH {
       delta_ = o.delta_;
       particles_ = o.particles_;
       boundary_ = o.boundary_;
+      motion_ = o.motion_;
     }
     return *this;
   }
@@ -343,15 +344,61 @@ class SPH {
   // A collider that wraps a distance volume: a particle closer than `Radius` to the surface is pushed out along the
   // volume's gradient and reflected with `Restitution` (include/dslsph.h: dsl_collider_set_volume).  Any volume will do,
   // MeshDistance's or one the host filled in.  It excludes a mesh list: set one or the other.
+  // The reference's collider interface expects movement (render/mesh/collider.go:10-36: Origin, UpdateOrigin, IsStatic).
+  // Motion is the rigid motion of the volume's own frame: `Rot` row-major, its columns the body's axes in world
+  // coordinates; `Origin` the body frame's origin; `LinVel` the body's velocity there and `AngVel` its angular velocity,
+  // world.  The voxels never move: UpdateOrigin / UpdateMotion hand 18 numbers to the next step
+  // (include/dslsph.h: dsl_collider_volume_motion).  The library does not integrate the pose.
   struct VolumeCollider {
     DistanceVolume Volume;
     float Radius = 0.f, Restitution = 0.f;
+    struct Motion {
+      float Rot[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+      float Origin[3] = {0.f, 0.f, 0.f}, LinVel[3] = {0.f, 0.f, 0.f}, AngVel[3] = {0.f, 0.f, 0.f};
+    };
+    struct Momentum {
+      float Impulse[3] = {0.f, 0.f, 0.f}, Torque[3] = {0.f, 0.f, 0.f};  // torque impulse about Motion::Origin
+    };
   };
   void Collider(const VolumeCollider& c) {
     ck(dsl_collider_set_volume(h_, nullptr, c.Volume.Values.data(), c.Volume.origin, c.Volume.step, c.Volume.dims, c.Radius,
                                c.Restitution, c.Volume.isUnsigned ? DSL_SDF_UNSIGNED : 0));
+    motion_ = VolumeCollider::Motion{};  // (a new volume starts where it was built, at rest: the library turns motion off)
   }
-  void RemoveVolumeCollider() { ck(dsl_collider_set_volume(h_, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0)); }
+  // The mirror keeps the motion last set, so that UpdateOrigin changes the origin alone.
+  void UpdateMotion(const VolumeCollider::Motion& m) {
+    ck(dsl_collider_volume_motion(h_, m.Rot, m.Origin, m.LinVel, m.AngVel));
+    motion_ = m;
+  }
+  // Collider.UpdateOrigin: the body frame's origin moves; orientation and velocities stay what UpdateMotion last set (the
+  // identity and zero after Collider, RemoveVolumeCollider or ClearMotion)
+  void UpdateOrigin(const float origin[3]) {
+    VolumeCollider::Motion m = motion_;
+    for (int a = 0; a < 3; ++a) m.Origin[a] = origin[a];
+    UpdateMotion(m);
+  }
+  // Collider.Origin
+  const VolumeCollider::Motion& Motion() const { return motion_; }
+  // back to Collider.IsStatic() == true: the static pass runs again
+  void ClearMotion() {
+    ck(dsl_collider_volume_motion(h_, nullptr, nullptr, nullptr, nullptr));
+    motion_ = VolumeCollider::Motion{};
+  }
+  bool IsStatic() {
+    double v = 0.0;
+    ck(dsl_get_option(h_, DSL_OPT_COLLIDER_VOLUME_MOVING, &v));
+    return v == 0.0;
+  }
+  // what the fluid handed to the body since the last reset (dsl_collider_volume_impulse): a host integrates the body with it
+  VolumeCollider::Momentum Impulse(bool reset = false) {
+    VolumeCollider::Momentum m;
+    ck(dsl_collider_volume_impulse(h_, m.Impulse, m.Torque, reset ? 1 : 0));
+    return m;
+  }
+  void RemoveVolumeCollider() {
+    ck(dsl_collider_set_volume(h_, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0));
+    motion_ = VolumeCollider::Motion{};
+  }
   // distance and unit gradient of the volume collider at every fluid particle (dsl_collider_volume_query)
   void ColliderDistances(std::vector<float>* dist, std::vector<float>* normal) {
     if (dist) dist->resize((size_t)particles_);
@@ -552,6 +599,7 @@ class SPH {
   dsl_handle* h_ = nullptr;
   float time_ = 0.0f, cache_life_ = CACHE_L, mu_ = VISCOSITY_WATER, delta_ = 0.0f;
   int particles_ = 0, boundary_ = 0;
+  VolumeCollider::Motion motion_{};  // the motion last handed to the library (UpdateMotion / UpdateOrigin)
 };
 
 }  // namespace sph

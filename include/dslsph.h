@@ -529,7 +529,41 @@ int dsl_collider_query(dsl_handle *h, int32_t *tri /* N: index or -1 */, float *
  * in dsl_wcsph_step, dsl_pcisph_step and DSL_PCI_END_STEP) and the skin step is not taken.  DSL_OPT_COLLIDE_HITS counts the
  * particles moved, DSL_K_COLLIDE times the launch.  Without a volume: no launch, no bit changes.
  * dsl_collider_volume_query: d and n of every fluid particle in host order (zeros where there is no cell, a zero normal
- * where |g| is not > 0), no response, whatever the radius; either pointer may be NULL.  Blocking.  Not in slab mode. */
+ * where |g| is not > 0), no response, whatever the radius; either pointer may be NULL.  Blocking.  Not in slab mode.
+ *
+ * dsl_collider_volume_motion: the volume collider as a rigid body in motion.  The voxels stay in the body's own frame, where
+ * they were built; the pose takes every particle into that frame and the normal back out of it.  rot: 9 floats, row-major R,
+ * whose columns are the body's axes in world coordinates; trans: the body frame's origin in world coordinates; lin_vel,
+ * ang_vel: the body's velocity at `trans` and its angular velocity, world.  A NULL pointer is the identity / zero; all four
+ * NULL: motion off, the static pass runs again.  The call does not synchronise and touches no device memory: the 18
+ * numbers go by value into each later launch, so a host calls it between steps as often as it likes.  The pose in force
+ * when a step driver is called holds for all nsteps of that call -- the library does not integrate the pose; a host that
+ * moves a body steps one at a time.  R is used as supplied, like the mesh collider's normals: not re-orthonormalised, not
+ * checked beyond being finite.  DSL_ERR_INVALID (dsl_last_error names the argument): no volume collider is set, a value is
+ * not finite.  DSL_ERR_UNSUPPORTED: a slab handle.  DSL_ERR_NOMEM: the sums' arrays (allocated when a motion is first set)
+ * could not be had; motion stays off.  A refused call changes nothing.  dsl_collider_set_volume -- a new volume or the
+ * removal -- turns motion off and zeroes the accumulators.  DSL_OPT_COLLIDER_VOLUME_MOVING is 1 while a motion is set.
+ *   Rule, per fluid particle at x with velocity v; float32, every operation rounded once, nothing fused, a dot product is
+ *   (a.x b.x + a.y b.y) + a.z b.z, the same in both math modes:  q = x - trans;  xl_a = (R[0][a] q.x + R[1][a] q.y) + R[2][a] q.z
+ *   (R^T q);  cell, d, g, |g|: the rule above evaluated at xl ("x is not finite" is tested on xl);  nl = g / |g|;
+ *   n_a = (R[a][0] nl.x + R[a][1] nl.y) + R[a][2] nl.z.  The particle collides when there is a cell, |g| > 0 and d < radius:
+ *   x <- x + (radius - d) n.  The body's velocity at the particle is u = lin_vel + ang_vel x q:
+ *   u.x = lin.x + (w.y q.z - w.z q.y), u.y and u.z its cyclic permutations, every product and difference rounded.
+ *   vn = (v - u).n; when vn < 0: f = (1 + restitution) vn, v <- v - f n, and the body receives the impulse J = (mass f) n,
+ *   mass f rounded first, and the torque impulse tau = q x J (tau.x = q.y J.z - q.z J.y and its cyclic permutations).  A
+ *   particle that is only pushed out (vn >= 0) hands over nothing: the position correction carries no momentum.  With the
+ *   identity, a zero translation and zero velocities every step is exact and the pass gives the static pass's bits.
+ *   The sums are reproducible, no float atomics: two runs give the same bytes.  Per slot s, in the order dsl_download_ids
+ *   reports, the contribution c_s has six components, J then tau, +0 for a slot that did not respond.  Workgroup b owns the
+ *   slots [256 b, 256 b + 256), slots past the last live one counting as +0; its partial is the tree
+ *   `for off in 128, 64, 32, 16, 8, 4, 2, 1: c[l] += c[l + off] for l < off`.  The pass total: lane l of one 256-lane
+ *   workgroup adds the partials l, l + 256, l + 512, ... in ascending order, starting from +0, and the same tree combines the
+ *   256 lane sums.  Then acc <- acc + total, once per pass, passes in stream order.
+ * While a motion is set dsl_collide_pass and the step drivers run this pass and its fold where they run the static pass
+ * (both timed under DSL_K_COLLIDE), and dsl_collider_volume_query returns d and the world-space n at the pose in force.
+ * dsl_collider_volume_impulse: what the fluid handed to the body since the last reset: impulse (3) and torque impulse
+ * about `trans` (3); either may be NULL.  Blocking.  reset = 1 zeroes the accumulators after the read.  Zeros while no
+ * motion has been set.  Not in slab mode. */
 #define DSL_SDF_UNSIGNED 1
 int dsl_mesh_distance_volume(dsl_handle *h, const float *vertices /* 9*T, host */, size_t n_triangles,
                              const float origin[3], const float step[3], const int32_t dims[3],
@@ -537,6 +571,9 @@ int dsl_mesh_distance_volume(dsl_handle *h, const float *vertices /* 9*T, host *
 int dsl_collider_set_volume(dsl_handle *h, const float *dev_volume, const float *host_volume, const float origin[3],
                             const float step[3], const int32_t dims[3], float radius, float restitution, int flags);
 int dsl_collider_volume_query(dsl_handle *h, float *dist /* N */, float *normal /* 3N */);
+int dsl_collider_volume_motion(dsl_handle *h, const float rot[9], const float trans[3],
+                               const float lin_vel[3], const float ang_vel[3]);
+int dsl_collider_volume_impulse(dsl_handle *h, float impulse[3], float torque[3], int reset);
 
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
@@ -856,7 +893,8 @@ enum {
   DSL_OPT_SDF_VISITS = 73,         /* (get, blocking) triangle visits: (voxel, triangle) pairs the distance phase tested */
   DSL_OPT_SDF_DISTANCE_MS = 74,    /* (get, blocking) milliseconds of its distance launch, as DSL_OPT_SURFACE_COUNT_MS; */
   DSL_OPT_SDF_SIGN_MS = 75,        /* its sign launches: the marks' memset, the sweep, the parity (0 with DSL_SDF_UNSIGNED) */
-  DSL_OPT_COLLIDER_VOLUME = 76     /* (get) voxels of the volume collider; 0: none */
+  DSL_OPT_COLLIDER_VOLUME = 76,    /* (get) voxels of the volume collider; 0: none */
+  DSL_OPT_COLLIDER_VOLUME_MOVING = 77   /* (get) 1 while a motion is set */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);

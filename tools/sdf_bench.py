@@ -13,6 +13,15 @@ Then the volume build itself on that lattice, band = 4 dx and band = +inf, ten t
 summed over the call's launches, the distance and sign phases, the bricks with a list and the triangle visits.
 
   python tools/sdf_bench.py [--n3 252] [--out profiles/sdf_16m.jsonl]
+
+--rigid: what a pose costs.  Two steps alternate instead, on fresh handles in this one process:
+
+  volume   as above: the static pass, k_collide_volume
+  rigid    the same volume with a motion set (dsl_collider_volume_motion): the sphere turned about its own centre, so that it
+           stands where the static one stands, with a linear and an angular velocity -- k_collide_volume_rigid and the fold of
+           its partial sums, two launches per step under DSL_K_COLLIDE (collide_ms_per_step is their sum)
+
+  python tools/sdf_bench.py --rigid [--n3 252] [--out profiles/sdf_rigid_16m.jsonl]
 """
 import argparse
 import json
@@ -32,6 +41,7 @@ def main():
     ap.add_argument("--level", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rigid", action="store_true", help="the static volume pass against the pass in rigid motion")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -75,14 +85,22 @@ def main():
         col_ms, launches = eng.timing("collide")
         return ms, col_ms, launches
 
+    def rigid_pose():
+        """0.7 rad about (1, 2, 3) through the sphere's centre: x = R (xl - c) + c"""
+        a = np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)
+        K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        R = (np.eye(3) + np.sin(0.7) * K + (1 - np.cos(0.7)) * (K @ K)).astype(np.float32)
+        c = np.array(center)
+        return dict(rot=R, trans=c - R.astype(np.float64) @ c, lin_vel=(0.3, -0.2, 0.1), ang_vel=(0.5, -1.0, 0.8))
+
     for rnd in range(args.rounds):
-        for kind in ("plain", "index", "volume"):
+        for kind in (("volume", "rigid") if args.rigid else ("plain", "index", "volume")):
             eng = fresh()
             extra = {}
             if kind == "index":
                 eng.set_option("collide_index", 1)
                 eng.set_collider_mesh(verts, normals, radius, 0.0)
-            elif kind == "volume":
+            elif kind in ("volume", "rigid"):
                 dvol = torch.empty(nvox, dtype=torch.float32, device="cuda")
                 eng.sync()
                 t0 = time.perf_counter()
@@ -90,14 +108,29 @@ def main():
                 eng.set_collider_volume(None, origin, dx, dims=dims, radius=radius, restitution=0.0, dev_volume=dvol.data_ptr())
                 extra = {"build_and_set_ms": round((time.perf_counter() - t0) * 1e3, 3), "dims": list(dims), "voxels": nvox,
                          "volume_bytes": 4 * nvox}
+                if kind == "rigid":
+                    eng.set_collider_volume_motion(**rigid_pose())
             ms, col_ms, launches = timed_steps(eng)
-            assert launches == (0 if kind == "plain" else args.steps)
+            per_step = {"plain": 0, "rigid": 2}.get(kind, 1)  # (the rigid pass and its fold)
+            assert launches == per_step * args.steps
             rec = {"config": kind, "round": rnd, "step_ms": round(ms, 4), "collide_ms_per_launch": round(col_ms, 4),
                    "hits_last_pass": eng.get_option("collide_hits"), **extra}
+            if args.rigid:
+                rec["collide_ms_per_step"] = round(col_ms * per_step, 4)
+            if kind == "rigid":
+                imp, trq = eng.collider_volume_impulse()
+                rec["impulse"], rec["torque"] = [float(v) for v in imp], [float(v) for v in trq]
             if kind == "index":
                 rec["visits_last_pass"] = eng.get_option("collide_visits")
             emit(rec)
             eng.close()
+
+    if args.rigid:
+        if args.out:
+            with open(args.out, "w") as f:
+                for rec in lines:
+                    f.write(json.dumps(rec) + "\n")
+        return
 
     # the build alone
     eng = fresh()
