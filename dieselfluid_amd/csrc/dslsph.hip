@@ -774,7 +774,7 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->col_hits);
   (void)hipFree(h->col_query);
   col_index_free(h);
-  (void)hipFree(h->vol_stage);
+  release(h->vol_stage);
   (void)hipFree(h->vol_ctr);
   surface_free(h);
   sdf_free(h);

@@ -10,6 +10,9 @@
 //   surface_mesh.hip   the indexed mesh: dsl_surface_extract_indexed, dsl_field_surface_indexed and their three kernels
 //   sdf.hip            implicit colliders: dsl_mesh_distance_volume, dsl_collider_set_volume, the volume collide pass, their kernels
 //   sdf_rigid.hip      the volume collider in rigid motion: dsl_collider_volume_motion, dsl_collider_volume_impulse, their two kernels
+// The last five are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
+// PhaseClock members): the lattice and its one check, the collider's cell evaluation, the arrays that grow on demand and the
+// per-phase event clocks.  The barrier with its LDS drain, the voxel coordinate and the ordered dot product are sph_device.hpp's.
 #pragma once
 
 #include "../../include/dslsph.h"
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "collide.hpp"
+#include "lattice.hpp"
 
 struct SlabLink;
 
@@ -176,65 +180,44 @@ struct dsl_handle {
   bool col_step_zeroed = false;
   // field volumes (volume.hip; dsl_field_volume).  vol_stage: the library's own output array of a host_out-only call (grows on
   // demand); vol_ctr: LDS / fallback / empty bricks and staged records of the last brick launch; vol_last_bricks: the last call ran the brick form
-  float* vol_stage = nullptr;
-  size_t vol_stage_count = 0;
+  dsl::DevArray<float> vol_stage;
   unsigned long long* vol_ctr = nullptr;
   bool vol_bricks = true;  // DSL_OPT_VOLUME_BRICKS (the measured choice: DESIGN.md 4.3)
   bool vol_last_bricks = false;
   // fluid surfaces (surface.hip; dsl_surface_extract).  surf_scan: one 64-bit count, then offset, per brick of 8 x 8 x 4 cubes and
   // the scan's upper levels behind them; surf_ctr: [0] triangles T, [1] bricks with a triangle, of the last call; surf_stage:
   // dsl_field_surface's triangles before they go to the host.  All three allocated on first use and grown on demand.
-  // surf_ev: the last call's phase boundaries (count | scan | . emit |) while timing is on; surf_timed: 0 none, 1 count and scan, 2 all
-  unsigned long long* surf_scan = nullptr;
-  size_t surf_scan_count = 0;
+  // surf_clock: the last call's phases count, scan and emit
+  dsl::DevArray<unsigned long long> surf_scan;
   unsigned long long* surf_ctr = nullptr;
-  float* surf_stage = nullptr;
-  size_t surf_stage_count = 0;
-  hipEvent_t surf_ev[5] = {};
-  int surf_timed = 0;
+  dsl::DevArray<float> surf_stage;
+  dsl::PhaseClock<3> surf_clock;
   // the indexed mesh (surface_mesh.hip; dsl_surface_extract_indexed).  mesh_words: one word per voxel, the voxel's vertex
   // prefix inside its brick of 8 x 8 x 4 voxels << 7 | its 7-bit edge mask; mesh_scan: count, then offset, per voxel brick and
   // the scan's upper levels; mesh_ctr: [0] vertices V of the last call; mesh_stage: dsl_field_surface_indexed's positions,
-  // normals and indices before they go to the host.  mesh_ev: vertex count | scan | vertex emit | index emit | while timing
-  // is on; mesh_timed: bit p = phase p was launched and marked
-  unsigned int* mesh_words = nullptr;
-  size_t mesh_words_count = 0;
-  unsigned long long* mesh_scan = nullptr;
-  size_t mesh_scan_count = 0;
+  // normals and indices before they go to the host.  mesh_clock: the phases vertex count, scan, vertex emit and index emit
+  dsl::DevArray<unsigned int> mesh_words;
+  dsl::DevArray<unsigned long long> mesh_scan;
   unsigned long long* mesh_ctr = nullptr;
-  float* mesh_stage = nullptr;
-  size_t mesh_stage_count = 0;
-  hipEvent_t mesh_ev[8] = {};
-  int mesh_timed = 0;
+  dsl::DevArray<float> mesh_stage;
+  dsl::PhaseClock<4> mesh_clock;
   // distance volumes of a mesh (sdf.hip; dsl_mesh_distance_volume), all allocated on first use and grown on demand.  sdf_stage:
   // the output of a host_out-only call; sdf_verts: the caller's vertices; sdf_rec / sdf_box: four float4 and six floats per
   // triangle; sdf_scan: one count, then offset, per brick of 8 x 8 x 4 voxels and the scan's upper levels; sdf_list: the
   // bricks' triangle lists; sdf_marks: one word per voxel, the sign sweep's marks; sdf_ctr: [0] bricks with a list, [1] triangle
-  // visits, [2] list entries of the last call.  sdf_ev: | distance | . | sign | while timing is on; sdf_timed: 0 none, 1 distance, 2 both
-  float* sdf_stage = nullptr;
-  size_t sdf_stage_count = 0;
-  float* sdf_verts = nullptr;
-  size_t sdf_verts_count = 0;
-  float4* sdf_rec = nullptr;
-  size_t sdf_rec_count = 0;
-  float* sdf_box = nullptr;
-  size_t sdf_box_count = 0;
-  unsigned long long* sdf_scan = nullptr;
-  size_t sdf_scan_count = 0;
-  int* sdf_list = nullptr;
-  size_t sdf_list_count = 0;
-  unsigned int* sdf_marks = nullptr;
-  size_t sdf_marks_count = 0;
+  // visits, [2] list entries of the last call.  sdf_clock: the phases distance and sign
+  dsl::DevArray<float> sdf_stage, sdf_verts, sdf_box;
+  dsl::DevArray<float4> sdf_rec;
+  dsl::DevArray<unsigned long long> sdf_scan;
+  dsl::DevArray<int> sdf_list;
+  dsl::DevArray<unsigned int> sdf_marks;
   unsigned long long* sdf_ctr = nullptr;
-  hipEvent_t sdf_ev[4] = {};
-  int sdf_timed = 0;
+  dsl::PhaseClock<2> sdf_clock;
   // the volume collider (sdf.hip; dsl_collider_set_volume): the library's copy of the volume and its lattice.  colv_on: set --
   // the collide pass runs k_collide_volume and a mesh is refused; colv_query: dsl_collider_volume_query's staging (4 words per particle)
-  float* colv_vol = nullptr;
-  size_t colv_count = 0;
+  dsl::DevArray<float> colv_vol;
   bool colv_on = false;
-  float colv_o[3] = {}, colv_s[3] = {};
-  int colv_n[3] = {};
+  dsl::Lattice colv_g{};
   float colv_radius = 0.0f, colv_rest = 0.0f;
   int colv_flags = 0;
   float* colv_query = nullptr;
@@ -244,8 +227,7 @@ struct dsl_handle {
   bool colv_moving = false;
   float colv_rot[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
   float colv_trans[3] = {}, colv_lin[3] = {}, colv_ang[3] = {};
-  float* colv_partial = nullptr;
-  size_t colv_partial_count = 0;
+  dsl::DevArray<float> colv_partial;
   float* colv_acc = nullptr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
@@ -382,25 +364,6 @@ size_t surf_scan_layout(long long n, std::vector<long long>* len, std::vector<si
 int surf_scan_run(dsl_handle* h, int kid, unsigned long long* s, const std::vector<long long>& len, const std::vector<size_t>& first,
                   unsigned long long* total_a, long long* total_b);
 int surf_read_ctr(dsl_handle* h, unsigned long long* two);
-
-// a library-owned device array that grows on demand and is counted in DSL_OPT_DEVICE_BYTES
-template <class T>
-int surf_reserve(dsl_handle* h, T** p, size_t* have, size_t want, const char* what) {
-  if (*have >= want) return DSL_OK;
-  (void)hipFree(*p);
-  h->dev_bytes -= *have * sizeof(T);
-  *p = nullptr;
-  *have = 0;
-  const hipError_t e = hipMalloc((void**)p, want * sizeof(T));
-  if (e != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();  // (the handle stays usable: the next launch check must not meet this error)
-    return fail(h, DSL_ERR_NOMEM, std::string(what) + ": hipMalloc: " + hipGetErrorString(e));
-  }
-  *have = want;
-  h->dev_bytes += want * sizeof(T);
-  return DSL_OK;
-}
 
 // ---- defined in surface_mesh.hip ----
 int surface_mesh_option(dsl_handle* h, int option, double* value);  // DSL_OPT_SURFACE_VERTICES and the mesh phases' ms (get)

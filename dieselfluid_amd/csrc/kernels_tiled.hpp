@@ -76,16 +76,8 @@ constexpr int kMetaInts = 376;
 static_assert(sizeof(TileMeta) == kMetaInts * sizeof(int), "TileMeta is copied as kMetaInts dwords");
 static_assert(kMetaInts % 4 == 0 && kMetaInts <= kTBlock, "one dword per lane of a 512-thread block, two of a 256-thread one");
 
-// __syncthreads() with the wave's own LDS traffic drained first, stated explicitly.  hipcc leaves the
-// `s_waitcnt lgkmcnt(0)` in front of an s_barrier to its waitcnt pass, and at the head of the double-buffered loops
-// below (LDS writes at the END of the loop body, the barrier at its HEAD, reached over the back edge) that pass
-// emitted none: the ISA had `ds_write_b128 ... s_branch ... s_barrier`.  A wave could then pass the barrier while a
-// sibling's last records or table words were still on their way, and one 16M run in three met a stale record
-// within a few thousand steps (densities off, then a blow-up): profiles/README.md, r03.
-__device__ __forceinline__ void sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
+// the tiled kernels' name for the barrier with its LDS drain (sph_device.hpp has the story)
+__device__ __forceinline__ void sync_lds() { lds_barrier(); }
 
 // (struct TileGrid: sph_device.hpp -- the host's handle holds one)
 __device__ __forceinline__ int tile_of_list_thread(const TileGrid& tg, int t) {

@@ -28,10 +28,8 @@ constexpr int kSdfBX = 8, kSdfBY = 8, kSdfBZ = 4;
 constexpr int kSdfChunk = 256;   // records per LDS chunk: 16 KiB
 constexpr int kSdfCounters = 4;  // [0] bricks with a non-empty list, [1] triangle visits (pairs tested), [2] list entries
 
-struct SdfLattice {
-  float o[3], s[3];
-  int n[3];
-  int nbx, nby, nbz;
+struct SdfLattice : Lattice {
+  int nbx, nby, nbz;  // bricks of 8 x 8 x 4 voxels per axis
 };
 // a, ab = b - a, ac = c - a, b, c: what the seven regions and the sweep need, the same whether computed once or per voxel
 struct alignas(16) SdfRec {
@@ -43,21 +41,11 @@ struct SdfBox {
 };
 struct ColVol {
   const float* vol;
-  float o[3], s[3];
-  int n[3];
+  Lattice g;
   float radius, rest;
 };
 
 namespace {
-// (sdf_rigid.hip keeps copies of sdf_sync_lds, sdf_dot and k_collide_volume's cell evaluation: a change to one belongs in both)
-__device__ __forceinline__ void sdf_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-__device__ __forceinline__ float sdf_coord(float o, float s, int i) { return __fadd_rn(o, __fmul_rn(s, (float)i)); }
-__device__ __forceinline__ float sdf_dot(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
 // how many of the axis' n coordinates are < v (STRICT) or <= v: the coordinate is monotone in the index, so a bisection on
 // the real coordinates decides it exactly, whatever the rounding of origin + step * idx.  0 for a NaN.
 template <bool STRICT>
@@ -65,7 +53,7 @@ __device__ __forceinline__ int sdf_count_below(float o, float s, int n, float v)
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    const float x = sdf_coord(o, s, mid);
+    const float x = lattice_coord(o, s, mid);
     if (STRICT ? x < v : x <= v) lo = mid + 1;
     else hi = mid;
   }
@@ -79,16 +67,16 @@ __device__ __forceinline__ float sdf_dist2(float px, float py, float pz, const f
   const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w, acz = r2.x;
   const float bx = r2.y, by = r2.z, bz = r2.w, cx = r3.x, cy = r3.y, cz = r3.z;
   float qx = ax, qy = ay, qz = az;
-  const float d1 = sdf_dot(abx, aby, abz, px - ax, py - ay, pz - az);
-  const float d2 = sdf_dot(acx, acy, acz, px - ax, py - ay, pz - az);
+  const float d1 = dot3(abx, aby, abz, px - ax, py - ay, pz - az);
+  const float d2 = dot3(acx, acy, acz, px - ax, py - ay, pz - az);
   if (!(d1 <= 0.f && d2 <= 0.f)) {
-    const float d3 = sdf_dot(abx, aby, abz, px - bx, py - by, pz - bz);
-    const float d4 = sdf_dot(acx, acy, acz, px - bx, py - by, pz - bz);
+    const float d3 = dot3(abx, aby, abz, px - bx, py - by, pz - bz);
+    const float d4 = dot3(acx, acy, acz, px - bx, py - by, pz - bz);
     if (d3 >= 0.f && d4 <= d3) {
       qx = bx, qy = by, qz = bz;
     } else {
-      const float d5 = sdf_dot(abx, aby, abz, px - cx, py - cy, pz - cz);
-      const float d6 = sdf_dot(acx, acy, acz, px - cx, py - cy, pz - cz);
+      const float d5 = dot3(abx, aby, abz, px - cx, py - cy, pz - cz);
+      const float d6 = dot3(acx, acy, acz, px - cx, py - cy, pz - cz);
       const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
       const float e1 = d4 - d3, e2 = d5 - d6;
       if (d6 >= 0.f && d5 <= d6) {
@@ -110,7 +98,7 @@ __device__ __forceinline__ float sdf_dist2(float px, float py, float pz, const f
     }
   }
   const float ex = px - qx, ey = py - qy, ez = pz - qz;
-  return sdf_dot(ex, ey, ez, ex, ey, ez);
+  return dot3(ex, ey, ez, ex, ey, ez);
 }
 }  // namespace
 
@@ -145,9 +133,9 @@ __global__ __launch_bounds__(kSdfBlock) void k_sdf_prep(int n_tri, const float* 
   }
   R.pad_ = 0.f;
   rec[t] = R;
-  const float d00 = sdf_dot(R.ab[0], R.ab[1], R.ab[2], R.ab[0], R.ab[1], R.ab[2]);
-  const float d01 = sdf_dot(R.ab[0], R.ab[1], R.ab[2], R.ac[0], R.ac[1], R.ac[2]);
-  const float d11 = sdf_dot(R.ac[0], R.ac[1], R.ac[2], R.ac[0], R.ac[1], R.ac[2]);
+  const float d00 = dot3(R.ab[0], R.ab[1], R.ab[2], R.ab[0], R.ab[1], R.ab[2]);
+  const float d01 = dot3(R.ab[0], R.ab[1], R.ab[2], R.ac[0], R.ac[1], R.ac[2]);
+  const float d11 = dot3(R.ac[0], R.ac[1], R.ac[2], R.ac[0], R.ac[1], R.ac[2]);
   const float p0 = d00 * d11, denom = p0 - d01 * d01;
   const float pad = 1.01f * band + 0.01f * ext + 1.0e-5f * big;
   bool reg = d00 > 0.f && d11 > 0.f && p0 < 1.0e30f && denom >= 1.0e-4f * p0;
@@ -173,8 +161,8 @@ __device__ __forceinline__ SdfBrick sdf_brick(const SdfLattice& g, int b) {
   K.nvox = 1;
   for (int a = 0; a < 3; ++a) {
     const int last = min(first[a] + edge[a], g.n[a]) - 1;
-    K.lo[a] = sdf_coord(g.o[a], g.s[a], first[a]);
-    K.hi[a] = sdf_coord(g.o[a], g.s[a], last);
+    K.lo[a] = lattice_coord(g.o[a], g.s[a], first[a]);
+    K.hi[a] = lattice_coord(g.o[a], g.s[a], last);
     K.nvox *= last - first[a] + 1;
   }
   return K;
@@ -227,7 +215,7 @@ __global__ __launch_bounds__(kSdfBlock) void k_sdf_distance(const float4* __rest
     if (mine) out[at] = band;
     return;
   }
-  const float px = sdf_coord(g.o[0], g.s[0], vi), py = sdf_coord(g.o[1], g.s[1], vj), pz = sdf_coord(g.o[2], g.s[2], vk);
+  const float px = lattice_coord(g.o[0], g.s[0], vi), py = lattice_coord(g.o[1], g.s[1], vj), pz = lattice_coord(g.o[2], g.s[2], vk);
   float best = INFINITY;
   for (unsigned long long base = first; base < end; base += kSdfChunk) {
     const int m = (int)min((unsigned long long)kSdfChunk, end - base);
@@ -238,12 +226,12 @@ __global__ __launch_bounds__(kSdfBlock) void k_sdf_distance(const float4* __rest
       s_rec[4 * tid + 2] = src[2];
       s_rec[4 * tid + 3] = src[3];
     }
-    sdf_sync_lds();
+    lds_barrier();
     for (int r = 0; r < m; ++r) {
       const float d2 = sdf_dist2(px, py, pz, s_rec[4 * r], s_rec[4 * r + 1], s_rec[4 * r + 2], s_rec[4 * r + 3]);
       if (d2 < best) best = d2;  // (NaN and +inf never win)
     }
-    sdf_sync_lds();  // (the next chunk overwrites the image)
+    lds_barrier();  // (the next chunk overwrites the image)
   }
   if (mine) out[at] = fminf(sqrtf(best), band);
 }
@@ -287,9 +275,9 @@ __global__ __launch_bounds__(kSdfBlock) void k_sdf_sweep(int n_tri, const SdfRec
     return pos ? (ev > 0.f || (ev == 0.f && dz <= 0.f)) : (ev < 0.f || (ev == 0.f && dz > 0.f));
   };
   for (int k = k0; k < k1; ++k) {
-    const float z = sdf_coord(g.o[2], g.s[2], k);
+    const float z = lattice_coord(g.o[2], g.s[2], k);
     for (int j = j0; j < j1; ++j) {
-      const float y = sdf_coord(g.o[1], g.s[1], j);
+      const float y = lattice_coord(g.o[1], g.s[1], j);
       if (!claims(dy0 * (z - lz0) - dz0 * (y - ly0), dz0, pos0)) continue;
       if (!claims(dy1 * (z - lz1) - dz1 * (y - ly1), dz1, pos1)) continue;
       if (!claims(dy2 * (z - lz2) - dz2 * (y - ly2), dz2, pos2)) continue;
@@ -329,32 +317,9 @@ __global__ __launch_bounds__(kSdfBlock) void k_collide_volume(int n, Bnd bnd, Co
   bool moved = false;
   if (live) {
     const float px = p.x[s], py = p.y[s], pz = p.z[s];
-    const float ux = (px - m.o[0]) / m.s[0], uy = (py - m.o[1]) / m.s[1], uz = (pz - m.o[2]) / m.s[2];
-    const float fx = floorf(ux), fy = floorf(uy), fz = floorf(uz);
-    // (false for NaN and the infinities)
-    bool cell = fx >= 0.f && fx <= (float)(m.n[0] - 2) && fy >= 0.f && fy <= (float)(m.n[1] - 2) && fz >= 0.f && fz <= (float)(m.n[2] - 2);
-    float d = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, mag = 0.f;
-    if (cell) {
-      const float tx = ux - fx, ty = uy - fy, tz = uz - fz;
-      const size_t nx = (size_t)m.n[0], nxy = nx * (size_t)m.n[1];
-      const float* c = m.vol + ((size_t)fz * nxy + (size_t)fy * nx + (size_t)fx);
-      const float c000 = c[0], c100 = c[1], c010 = c[nx], c110 = c[nx + 1];
-      const float c001 = c[nxy], c101 = c[nxy + 1], c011 = c[nxy + nx], c111 = c[nxy + nx + 1];
-      cell = isfinite(c000) && isfinite(c100) && isfinite(c010) && isfinite(c110) && isfinite(c001) && isfinite(c101) &&
-             isfinite(c011) && isfinite(c111);
-      auto lerp = [](float a, float b, float t) { return a + t * (b - a); };
-      const float e00 = lerp(c000, c100, tx), e10 = lerp(c010, c110, tx), e01 = lerp(c001, c101, tx), e11 = lerp(c011, c111, tx);
-      const float f0 = lerp(e00, e10, ty), f1 = lerp(e01, e11, ty);
-      d = lerp(f0, f1, tz);
-      gz = (f1 - f0) / m.s[2];
-      gy = (lerp(e10, e11, tz) - lerp(e00, e01, tz)) / m.s[1];
-      const float x0 = lerp(lerp(c000, c010, ty), lerp(c001, c011, ty), tz);
-      const float x1 = lerp(lerp(c100, c110, ty), lerp(c101, c111, ty), tz);
-      gx = (x1 - x0) / m.s[0];
-      mag = sqrtf(sdf_dot(gx, gy, gz, gx, gy, gz));
-    }
-    const bool has_n = cell && mag > 0.f;
-    const float nx_ = gx / mag, ny_ = gy / mag, nz_ = gz / mag;
+    const CellEval e = volume_cell_eval(m.g, m.vol, px, py, pz);
+    const bool cell = e.cell, has_n = cell && e.mag > 0.f;
+    const float d = e.d, nx_ = e.gx / e.mag, ny_ = e.gy / e.mag, nz_ = e.gz / e.mag;
     if constexpr (RESPOND) {
       moved = has_n && d < m.radius;
       if (moved) {
@@ -363,7 +328,7 @@ __global__ __launch_bounds__(kSdfBlock) void k_collide_volume(int n, Bnd bnd, Co
         p.y[s] = py + pen * ny_;
         p.z[s] = pz + pen * nz_;
         const float vx = v.x[s], vy = v.y[s], vz = v.z[s];
-        const float vn = sdf_dot(vx, vy, vz, nx_, ny_, nz_);
+        const float vn = dot3(vx, vy, vz, nx_, ny_, nz_);
         if (vn < 0.f) {
           const float f = (1.0f + m.rest) * vn;
           v.x[s] = vx - f * nx_;
@@ -391,25 +356,13 @@ __global__ __launch_bounds__(kSdfBlock) void k_collide_volume(int n, Bnd bnd, Co
 // host side
 // ---------------------------------------------------------------------------------------
 namespace {
-void sdf_mark(dsl_handle* h, int k) {
-  if (h->timing != 1) return;
-  if (!h->sdf_ev[k]) (void)hipEventCreate(&h->sdf_ev[k]);
-  (void)hipEventRecord(h->sdf_ev[k], h->stream);
-}
-ColVol col_vol(const dsl_handle* h) {
-  ColVol m;
-  m.vol = h->colv_vol;
-  for (int a = 0; a < 3; ++a) m.o[a] = h->colv_o[a], m.s[a] = h->colv_s[a], m.n[a] = h->colv_n[a];
-  m.radius = h->colv_radius;
-  m.rest = h->colv_rest;
-  return m;
-}
+ColVol col_vol(const dsl_handle* h) { return ColVol{h->colv_vol.p, h->colv_g, h->colv_radius, h->colv_rest}; }
 }  // namespace
 
 int sdf_option(dsl_handle* h, int option, double* value) {
   *value = 0.0;
   if (option == DSL_OPT_COLLIDER_VOLUME) {
-    *value = h->colv_on ? (double)h->colv_n[0] * h->colv_n[1] * h->colv_n[2] : 0.0;
+    *value = h->colv_on ? (double)h->colv_g.n[0] * h->colv_g.n[1] * h->colv_g.n[2] : 0.0;
     return DSL_OK;
   }
   if (option == DSL_OPT_COLLIDER_VOLUME_MOVING) {
@@ -426,29 +379,22 @@ int sdf_option(dsl_handle* h, int option, double* value) {
     return DSL_OK;
   }
   // the last call's phases, from device events of their own (recorded while dsl_timing_enable(1) holds)
-  const int k = option == DSL_OPT_SDF_DISTANCE_MS ? 0 : 2;
-  if (h->sdf_timed == 0 || (k == 2 && h->sdf_timed < 2)) return DSL_OK;
-  HIP_TRY(h, hipEventSynchronize(h->sdf_ev[k + 1]));
-  float ms = 0.f;
-  HIP_TRY(h, hipEventElapsedTime(&ms, h->sdf_ev[k], h->sdf_ev[k + 1]));
-  *value = (double)ms;
-  return DSL_OK;
+  return h->sdf_clock.ms(h, option == DSL_OPT_SDF_DISTANCE_MS ? 0 : 1, value);
 }
 
 void sdf_free(dsl_handle* h) {
-  (void)hipFree(h->sdf_stage);
-  (void)hipFree(h->sdf_verts);
-  (void)hipFree(h->sdf_rec);
-  (void)hipFree(h->sdf_box);
-  (void)hipFree(h->sdf_scan);
+  release(h->sdf_stage);
+  release(h->sdf_verts);
+  release(h->sdf_rec);
+  release(h->sdf_box);
+  release(h->sdf_scan);
   (void)hipFree(h->sdf_ctr);
-  (void)hipFree(h->sdf_list);
-  (void)hipFree(h->sdf_marks);
-  (void)hipFree(h->colv_vol);
+  release(h->sdf_list);
+  release(h->sdf_marks);
+  release(h->colv_vol);
   (void)hipFree(h->colv_query);
   sdf_rigid_free(h);
-  for (hipEvent_t e : h->sdf_ev)
-    if (e) (void)hipEventDestroy(e);
+  h->sdf_clock.destroy();
 }
 
 // The volume branch of the collide pass: in place on the current state.  dsl_stats.max_vel / max_f stay what Update saw.
@@ -477,19 +423,9 @@ int dsl_mesh_distance_volume(dsl_handle* h, const float* vertices, size_t n_tria
   // every refusal comes before anything is touched
   if (!vertices || n_triangles == 0) return fail(h, DSL_ERR_INVALID, w + ": vertices must not be NULL and n_triangles must be > 0");
   if (n_triangles > ((size_t)1 << 24)) return fail(h, DSL_ERR_INVALID, w + ": more than 2^24 triangles");
-  if (!origin || !step || !dims) return fail(h, DSL_ERR_INVALID, w + ": origin, step and dims must not be NULL");
   SdfLattice g;
-  long long nvox = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1) return fail(h, DSL_ERR_INVALID, w + ": every entry of dims must be >= 1");
-    nvox *= dims[a];  // (each factor < 2^31 and the running product is checked: no overflow)
-    if (nvox > (1ll << 30)) return fail(h, DSL_ERR_INVALID, w + ": dims holds more than 2^30 voxels");
-    if (!(std::isfinite(step[a]) && step[a] > 0.0f)) return fail(h, DSL_ERR_INVALID, w + ": every entry of step must be finite and > 0");
-    if (!std::isfinite(origin[a])) return fail(h, DSL_ERR_INVALID, w + ": every entry of origin must be finite");
-    g.o[a] = origin[a];
-    g.s[a] = step[a];
-    g.n[a] = dims[a];
-  }
+  long long nvox = 0;
+  if (int rc = lattice_check(h, w, origin, step, dims, 1, &g, &nvox)) return rc;
   if (!(band > 0.0f)) return fail(h, DSL_ERR_INVALID, w + ": band must be > 0 (+inf is allowed)");
   if (flags & ~DSL_SDF_UNSIGNED) return fail(h, DSL_ERR_INVALID, w + ": unknown bits in flags");
   if (!dev_out && !host_out) return fail(h, DSL_ERR_INVALID, w + ": dev_out and host_out are both NULL");
@@ -502,65 +438,62 @@ int dsl_mesh_distance_volume(dsl_handle* h, const float* vertices, size_t n_tria
 
   float* out = dev_out;
   if (!out) {
-    if (int rc = surf_reserve(h, &h->sdf_stage, &h->sdf_stage_count, (size_t)nvox, "dsl_mesh_distance_volume: the staging array")) return rc;
-    out = h->sdf_stage;
+    if (int rc = reserve(h, h->sdf_stage, (size_t)nvox, "dsl_mesh_distance_volume: the staging array")) return rc;
+    out = h->sdf_stage.p;
   }
   std::vector<long long> len;
   std::vector<size_t> first;
   const size_t scan_all = surf_scan_layout(nb, &len, &first);
-  if (int rc = surf_reserve(h, &h->sdf_verts, &h->sdf_verts_count, (size_t)9 * T, "dsl_mesh_distance_volume: the vertex array")) return rc;
-  if (int rc = surf_reserve(h, &h->sdf_rec, &h->sdf_rec_count, (size_t)4 * T, "dsl_mesh_distance_volume: the triangle records")) return rc;
-  if (int rc = surf_reserve(h, &h->sdf_box, &h->sdf_box_count, (size_t)6 * T, "dsl_mesh_distance_volume: the triangle boxes")) return rc;
-  if (int rc = surf_reserve(h, &h->sdf_scan, &h->sdf_scan_count, scan_all, "dsl_mesh_distance_volume: the scan array")) return rc;
+  if (int rc = reserve(h, h->sdf_verts, (size_t)9 * T, "dsl_mesh_distance_volume: the vertex array")) return rc;
+  if (int rc = reserve(h, h->sdf_rec, (size_t)4 * T, "dsl_mesh_distance_volume: the triangle records")) return rc;
+  if (int rc = reserve(h, h->sdf_box, (size_t)6 * T, "dsl_mesh_distance_volume: the triangle boxes")) return rc;
+  if (int rc = reserve(h, h->sdf_scan, scan_all, "dsl_mesh_distance_volume: the scan array")) return rc;
   if (!h->sdf_ctr)
     if (int rc = dev_alloc(h, &h->sdf_ctr, kSdfCounters)) return rc;
-  SdfRec* rec = reinterpret_cast<SdfRec*>(h->sdf_rec);
-  SdfBox* box = reinterpret_cast<SdfBox*>(h->sdf_box);
+  SdfRec* rec = reinterpret_cast<SdfRec*>(h->sdf_rec.p);
+  SdfBox* box = reinterpret_cast<SdfBox*>(h->sdf_box.p);
   const dim3 block(kSdfBlock);
   const dim3 tri_grid((unsigned)((T + kSdfBlock - 1) / kSdfBlock)), brick_grid((unsigned)((nb + kSdfBlock - 1) / kSdfBlock));
 
-  h->sdf_timed = 0;
-  HIP_TRY(h, hipMemcpyAsync(h->sdf_verts, vertices, (size_t)9 * T * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  h->sdf_clock.reset();
+  HIP_TRY(h, hipMemcpyAsync(h->sdf_verts.p, vertices, (size_t)9 * T * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->sdf_ctr, 0, kSdfCounters * sizeof(unsigned long long), h->stream));
-  int rc = timed(h, DSL_K_SDF, [&] { hipLaunchKernelGGL(k_sdf_prep, tri_grid, block, 0, h->stream, T, h->sdf_verts, band, rec, box); });
+  int rc = timed(h, DSL_K_SDF, [&] { hipLaunchKernelGGL(k_sdf_prep, tri_grid, block, 0, h->stream, T, h->sdf_verts.p, band, rec, box); });
   if (rc) return rc;
   rc = timed(h, DSL_K_SDF, [&] {
-    hipLaunchKernelGGL(k_sdf_brick_count, brick_grid, block, 0, h->stream, T, box, g, nb, h->sdf_scan, h->sdf_ctr);
+    hipLaunchKernelGGL(k_sdf_brick_count, brick_grid, block, 0, h->stream, T, box, g, nb, h->sdf_scan.p, h->sdf_ctr);
   });
   if (rc) return rc;
-  if ((rc = surf_scan_run(h, DSL_K_SDF, h->sdf_scan, len, first, h->sdf_ctr + 2, nullptr))) return rc;
+  if ((rc = surf_scan_run(h, DSL_K_SDF, h->sdf_scan.p, len, first, h->sdf_ctr + 2, nullptr))) return rc;
   // the lists' length decides their allocation: one blocking read (it also ends the use of `vertices`)
   unsigned long long ctr[kSdfCounters] = {};
   HIP_TRY(h, hipMemcpyAsync(ctr, h->sdf_ctr, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (int rc2 = surf_reserve(h, &h->sdf_list, &h->sdf_list_count, (size_t)std::max<unsigned long long>(ctr[2], 1),
-                             "dsl_mesh_distance_volume: the brick lists"))
+  if (int rc2 = reserve(h, h->sdf_list, (size_t)std::max<unsigned long long>(ctr[2], 1), "dsl_mesh_distance_volume: the brick lists"))
     return rc2;
   rc = timed(h, DSL_K_SDF, [&] {
-    hipLaunchKernelGGL(k_sdf_brick_fill, brick_grid, block, 0, h->stream, T, box, g, nb, h->sdf_scan, h->sdf_list);
+    hipLaunchKernelGGL(k_sdf_brick_fill, brick_grid, block, 0, h->stream, T, box, g, nb, h->sdf_scan.p, h->sdf_list.p);
   });
   if (rc) return rc;
-  sdf_mark(h, 0);
+  h->sdf_clock.begin(h, 0);
   rc = timed(h, DSL_K_SDF, [&] {
-    hipLaunchKernelGGL(k_sdf_distance, dim3((unsigned)nb), block, 0, h->stream, reinterpret_cast<const float4*>(h->sdf_rec), g, nb,
-                       h->sdf_scan, h->sdf_ctr, h->sdf_list, band, out);
+    hipLaunchKernelGGL(k_sdf_distance, dim3((unsigned)nb), block, 0, h->stream, reinterpret_cast<const float4*>(h->sdf_rec.p), g, nb,
+                       h->sdf_scan.p, h->sdf_ctr, h->sdf_list.p, band, out);
   });
   if (rc) return rc;
-  sdf_mark(h, 1);
-  h->sdf_timed = h->timing == 1 ? 1 : 0;
+  h->sdf_clock.end(h, 0);
   if (!(flags & DSL_SDF_UNSIGNED)) {
-    if (int rc2 = surf_reserve(h, &h->sdf_marks, &h->sdf_marks_count, (size_t)nvox, "dsl_mesh_distance_volume: the marks")) return rc2;
-    HIP_TRY(h, hipMemsetAsync(h->sdf_marks, 0, (size_t)nvox * sizeof(unsigned int), h->stream));
-    sdf_mark(h, 2);
-    rc = timed(h, DSL_K_SDF, [&] { hipLaunchKernelGGL(k_sdf_sweep, tri_grid, block, 0, h->stream, T, rec, g, h->sdf_marks); });
+    if (int rc2 = reserve(h, h->sdf_marks, (size_t)nvox, "dsl_mesh_distance_volume: the marks")) return rc2;
+    HIP_TRY(h, hipMemsetAsync(h->sdf_marks.p, 0, (size_t)nvox * sizeof(unsigned int), h->stream));
+    h->sdf_clock.begin(h, 1);
+    rc = timed(h, DSL_K_SDF, [&] { hipLaunchKernelGGL(k_sdf_sweep, tri_grid, block, 0, h->stream, T, rec, g, h->sdf_marks.p); });
     if (rc) return rc;
     const int nrows = (int)(nvox / g.n[0]), per = kSdfBlock / kWave;
     rc = timed(h, DSL_K_SDF, [&] {
-      hipLaunchKernelGGL(k_sdf_sign, dim3((unsigned)((nrows + per - 1) / per)), block, 0, h->stream, g, nrows, h->sdf_marks, out);
+      hipLaunchKernelGGL(k_sdf_sign, dim3((unsigned)((nrows + per - 1) / per)), block, 0, h->stream, g, nrows, h->sdf_marks.p, out);
     });
     if (rc) return rc;
-    sdf_mark(h, 3);
-    if (h->sdf_timed == 1) h->sdf_timed = 2;
+    h->sdf_clock.end(h, 1);
   }
   if (host_out) {
     HIP_TRY(h, hipMemcpyAsync(host_out, out, (size_t)nvox * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -584,25 +517,20 @@ int dsl_collider_set_volume(dsl_handle* h, const float* dev_volume, const float*
                                         "remove the mesh first (dsl_collider_set_mesh with n_triangles = 0)");
   if ((dev_volume != nullptr) == (host_volume != nullptr)) return fail(h, DSL_ERR_INVALID, w + ": exactly one of dev_volume and host_volume must be given");
   if (!origin || !step) return fail(h, DSL_ERR_INVALID, w + ": origin and step must not be NULL");
-  long long nvox = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 2) return fail(h, DSL_ERR_INVALID, w + ": every entry of dims must be >= 2");
-    nvox *= dims[a];
-    if (nvox > (1ll << 30)) return fail(h, DSL_ERR_INVALID, w + ": dims holds more than 2^30 voxels");
-    if (!(std::isfinite(step[a]) && step[a] > 0.0f)) return fail(h, DSL_ERR_INVALID, w + ": every entry of step must be finite and > 0");
-    if (!std::isfinite(origin[a])) return fail(h, DSL_ERR_INVALID, w + ": every entry of origin must be finite");
-  }
+  Lattice g;  // (the handle keeps the old lattice until the new collider is whole)
+  long long nvox = 0;
+  if (int rc = lattice_check(h, w, origin, step, dims, 2, &g, &nvox)) return rc;
   if (flags & ~DSL_SDF_UNSIGNED) return fail(h, DSL_ERR_INVALID, w + ": unknown bits in flags");
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (a pass in flight may still read the volume that is replaced)
   h->colv_on = false;  // no collider until the new one is whole
   if (int rc = collide_volume_rigid_reset(h)) return rc;  // ... and a new volume starts at rest, with nothing handed over
-  if (int rc = surf_reserve(h, &h->colv_vol, &h->colv_count, (size_t)nvox, "dsl_collider_set_volume: the volume")) return rc;
+  if (int rc = reserve(h, h->colv_vol, (size_t)nvox, "dsl_collider_set_volume: the volume")) return rc;
   if (!h->col_hits)
     if (int rc = dev_alloc(h, &h->col_hits, 1)) return rc;
-  HIP_TRY(h, hipMemcpyAsync(h->colv_vol, dev_volume ? dev_volume : host_volume, (size_t)nvox * sizeof(float),
+  HIP_TRY(h, hipMemcpyAsync(h->colv_vol.p, dev_volume ? dev_volume : host_volume, (size_t)nvox * sizeof(float),
                             dev_volume ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the caller's array is never retained after the call returns)
-  for (int a = 0; a < 3; ++a) h->colv_o[a] = origin[a], h->colv_s[a] = step[a], h->colv_n[a] = dims[a];
+  h->colv_g = g;
   h->colv_radius = radius;
   h->colv_rest = restitution;
   h->colv_flags = flags;

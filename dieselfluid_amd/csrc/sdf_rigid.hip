@@ -2,7 +2,7 @@
 // pass and the query of sdf.hip with the particle taken into the body's frame and the normal back out of it, the response
 // against the body's surface velocity, and the momentum the fluid hands to the body.  A translation unit of its own, so
 // that sdf.hip's kernels come out as they are; its kernel list is tests/golden/device_kernels_sdf_rigid.txt.  The cell
-// evaluation restates k_collide_volume's (sdf.hip) line for line.  Same flags as every unit: -ffp-contract=off keeps every
+// evaluation is k_collide_volume's (lattice.hpp: volume_cell_eval).  Same flags as every unit: -ffp-contract=off keeps every
 // operation at one rounding, `/` and sqrtf are the correctly rounded ones.  The rule is build-defined (include/dslsph.h,
 // DESIGN.md 4.6) and restated operation for operation in tests/sdf_rigid_ref.py; it is the same in both math modes.
 //
@@ -22,23 +22,12 @@ constexpr int kRigidBlock = 256;
 // the lattice and the response's constants, then the motion: all by value, wave-uniform
 struct RigidVol {
   const float* vol;
-  float o[3], s[3];
-  int n[3];
+  Lattice g;
   float radius, rest, mass;
   float rot[9], trans[3], lin[3], ang[3];
 };
 
 namespace {
-// (second copies of sdf.hip's sdf_sync_lds and sdf_dot, kept here so that sdf.hip's kernels come out untouched: a change
-// to the LDS-drain idiom or to the dot product's order belongs in both units)
-__device__ __forceinline__ void rigid_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-__device__ __forceinline__ float rigid_dot(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
 // The tree of include/dslsph.h over the workgroup's 256 values per component: for off in 128, 64, ..., 1: c[l] += c[l + off]
 // for l < off.  Offsets 128 and 64 through LDS -- lane l < 64 forms (c[l] + c[l + 128]) + (c[l + 64] + c[l + 192]), which is
 // what the two steps leave in c[l] -- the rest by __shfl_down inside wave 0, whose lane 0 ends with the sums.
@@ -46,7 +35,7 @@ __device__ __forceinline__ void rigid_tree(float (&c)[6], float* lds) {
   const int tid = threadIdx.x;
 #pragma unroll
   for (int k = 0; k < 6; ++k) lds[k * kRigidBlock + tid] = c[k];
-  rigid_sync_lds();
+  lds_barrier();
   if (tid < kWave) {  // (wave-uniform)
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -76,40 +65,16 @@ __global__ __launch_bounds__(kRigidBlock) void k_collide_volume_rigid(int n, int
     const float px = p.x[s], py = p.y[s], pz = p.z[s];
     const float qx = px - m.trans[0], qy = py - m.trans[1], qz = pz - m.trans[2];
     // xl = R^T q
-    const float lx = rigid_dot(m.rot[0], m.rot[3], m.rot[6], qx, qy, qz);
-    const float ly = rigid_dot(m.rot[1], m.rot[4], m.rot[7], qx, qy, qz);
-    const float lz = rigid_dot(m.rot[2], m.rot[5], m.rot[8], qx, qy, qz);
-    // ---- k_collide_volume's cell evaluation at xl (sdf.hip; tests/sdf_ref.py: collider_eval) ----
-    const float ux = (lx - m.o[0]) / m.s[0], uy = (ly - m.o[1]) / m.s[1], uz = (lz - m.o[2]) / m.s[2];
-    const float fx = floorf(ux), fy = floorf(uy), fz = floorf(uz);
-    // (false for NaN and the infinities)
-    bool cell = fx >= 0.f && fx <= (float)(m.n[0] - 2) && fy >= 0.f && fy <= (float)(m.n[1] - 2) && fz >= 0.f && fz <= (float)(m.n[2] - 2);
-    float d = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, mag = 0.f;
-    if (cell) {
-      const float tx = ux - fx, ty = uy - fy, tz = uz - fz;
-      const size_t nx = (size_t)m.n[0], nxy = nx * (size_t)m.n[1];
-      const float* cc = m.vol + ((size_t)fz * nxy + (size_t)fy * nx + (size_t)fx);
-      const float c000 = cc[0], c100 = cc[1], c010 = cc[nx], c110 = cc[nx + 1];
-      const float c001 = cc[nxy], c101 = cc[nxy + 1], c011 = cc[nxy + nx], c111 = cc[nxy + nx + 1];
-      cell = isfinite(c000) && isfinite(c100) && isfinite(c010) && isfinite(c110) && isfinite(c001) && isfinite(c101) &&
-             isfinite(c011) && isfinite(c111);
-      auto lerp = [](float a, float b, float t) { return a + t * (b - a); };
-      const float e00 = lerp(c000, c100, tx), e10 = lerp(c010, c110, tx), e01 = lerp(c001, c101, tx), e11 = lerp(c011, c111, tx);
-      const float f0 = lerp(e00, e10, ty), f1 = lerp(e01, e11, ty);
-      d = lerp(f0, f1, tz);
-      gz = (f1 - f0) / m.s[2];
-      gy = (lerp(e10, e11, tz) - lerp(e00, e01, tz)) / m.s[1];
-      const float x0 = lerp(lerp(c000, c010, ty), lerp(c001, c011, ty), tz);
-      const float x1 = lerp(lerp(c100, c110, ty), lerp(c101, c111, ty), tz);
-      gx = (x1 - x0) / m.s[0];
-      mag = sqrtf(rigid_dot(gx, gy, gz, gx, gy, gz));
-    }
-    const bool has_n = cell && mag > 0.f;
-    const float lnx = gx / mag, lny = gy / mag, lnz = gz / mag;
+    const float lx = dot3(m.rot[0], m.rot[3], m.rot[6], qx, qy, qz);
+    const float ly = dot3(m.rot[1], m.rot[4], m.rot[7], qx, qy, qz);
+    const float lz = dot3(m.rot[2], m.rot[5], m.rot[8], qx, qy, qz);
+    const CellEval e = volume_cell_eval(m.g, m.vol, lx, ly, lz);
+    const bool cell = e.cell, has_n = cell && e.mag > 0.f;
+    const float d = e.d, lnx = e.gx / e.mag, lny = e.gy / e.mag, lnz = e.gz / e.mag;
     // n = R nl
-    const float nx_ = rigid_dot(m.rot[0], m.rot[1], m.rot[2], lnx, lny, lnz);
-    const float ny_ = rigid_dot(m.rot[3], m.rot[4], m.rot[5], lnx, lny, lnz);
-    const float nz_ = rigid_dot(m.rot[6], m.rot[7], m.rot[8], lnx, lny, lnz);
+    const float nx_ = dot3(m.rot[0], m.rot[1], m.rot[2], lnx, lny, lnz);
+    const float ny_ = dot3(m.rot[3], m.rot[4], m.rot[5], lnx, lny, lnz);
+    const float nz_ = dot3(m.rot[6], m.rot[7], m.rot[8], lnx, lny, lnz);
     if constexpr (RESPOND) {
       moved = has_n && d < m.radius;
       if (moved) {
@@ -122,7 +87,7 @@ __global__ __launch_bounds__(kRigidBlock) void k_collide_volume_rigid(int n, int
         const float by = m.lin[1] + (m.ang[2] * qx - m.ang[0] * qz);
         const float bz = m.lin[2] + (m.ang[0] * qy - m.ang[1] * qx);
         const float vx = v.x[s], vy = v.y[s], vz = v.z[s];
-        const float vn = rigid_dot(vx - bx, vy - by, vz - bz, nx_, ny_, nz_);
+        const float vn = dot3(vx - bx, vy - by, vz - bz, nx_, ny_, nz_);
         if (vn < 0.f) {
           responded = true;
           const float f = (1.0f + m.rest) * vn;
@@ -193,11 +158,9 @@ __global__ __launch_bounds__(kRigidBlock) void k_colv_impulse_fold(int nb, const
 namespace {
 RigidVol rigid_vol(const dsl_handle* h) {
   RigidVol m;
-  m.vol = h->colv_vol;
-  for (int a = 0; a < 3; ++a) {
-    m.o[a] = h->colv_o[a], m.s[a] = h->colv_s[a], m.n[a] = h->colv_n[a];
-    m.trans[a] = h->colv_trans[a], m.lin[a] = h->colv_lin[a], m.ang[a] = h->colv_ang[a];
-  }
+  m.vol = h->colv_vol.p;
+  m.g = h->colv_g;
+  for (int a = 0; a < 3; ++a) m.trans[a] = h->colv_trans[a], m.lin[a] = h->colv_lin[a], m.ang[a] = h->colv_ang[a];
   for (int a = 0; a < 9; ++a) m.rot[a] = h->colv_rot[a];
   m.radius = h->colv_radius;
   m.rest = h->colv_rest;
@@ -208,8 +171,7 @@ inline int rigid_blocks(int n) { return (n + kRigidBlock - 1) / kRigidBlock; }
 
 // partial[6][ceil(cap / 256)] and the six accumulator words, the library's own
 int rigid_reserve(dsl_handle* h) {
-  if (int rc = surf_reserve(h, &h->colv_partial, &h->colv_partial_count, (size_t)6 * rigid_blocks(h->cap), "dsl_collider_volume_motion: the partial sums"))
-    return rc;
+  if (int rc = reserve(h, h->colv_partial, (size_t)6 * rigid_blocks(h->cap), "dsl_collider_volume_motion: the partial sums")) return rc;
   if (!h->colv_acc)
     if (int rc = dev_alloc(h, &h->colv_acc, 6)) return rc;  // (zeroed)
   return DSL_OK;
@@ -217,7 +179,7 @@ int rigid_reserve(dsl_handle* h) {
 }  // namespace
 
 void sdf_rigid_free(dsl_handle* h) {
-  (void)hipFree(h->colv_partial);
+  release(h->colv_partial);
   (void)hipFree(h->colv_acc);
 }
 
@@ -231,17 +193,17 @@ int collide_volume_rigid_reset(dsl_handle* h) {
 // The collide pass while a motion is set: the rigid pass, then the fold, in place on the current state.
 int collide_volume_rigid_pass(dsl_handle* h) {
   const int nb = rigid_blocks(h->n);
-  if ((size_t)6 * nb > h->colv_partial_count)  // (the arrays cover the capacity: n never exceeds it)
+  if ((size_t)6 * nb > h->colv_partial.count)  // (the arrays cover the capacity: n never exceeds it)
     if (int rc = rigid_reserve(h)) return rc;
   HIP_TRY(h, hipMemsetAsync(h->col_hits, 0, sizeof(int), h->stream));
   int rc = timed(h, DSL_K_COLLIDE, [&] {
     hipLaunchKernelGGL(k_collide_volume_rigid<true>, dim3((unsigned)nb), dim3(kRigidBlock), 0, h->stream, h->n, nb, bnd_of(h),
                        rigid_vol(h), mpos(h, h->cur_pv), mvel(h, h->cur_pv), (float*)nullptr, (float*)nullptr, (const int*)nullptr,
-                       h->col_hits, h->colv_partial);
+                       h->col_hits, h->colv_partial.p);
   });
   if (rc) return rc;
   rc = timed(h, DSL_K_COLLIDE, [&] {
-    hipLaunchKernelGGL(k_colv_impulse_fold, dim3(1), dim3(kRigidBlock), 0, h->stream, nb, (const float*)h->colv_partial, h->colv_acc);
+    hipLaunchKernelGGL(k_colv_impulse_fold, dim3(1), dim3(kRigidBlock), 0, h->stream, nb, (const float*)h->colv_partial.p, h->colv_acc);
   });
   if (rc) return rc;
   h->grid_valid = false;  // positions moved

@@ -6,14 +6,6 @@
 
 namespace dsl {
 
-namespace {
-// the barrier with its LDS drain stated (as kernels_tiled.hpp's: tools/isa_audit.py keeps it that way)
-__device__ __forceinline__ void bal_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-}  // namespace
-
 // One lane per live slot, grid-stride.  The slots are cell-sorted (the appended ghosts and migrants behind them are in
 // band order), so the lanes of a wave mostly share a layer: equal-layer runs are found with one ballot, as k_cell_rank
 // finds its equal-cell runs, and only a run's first lane adds -- the run's length -- to the workgroup's histogram in
@@ -23,7 +15,7 @@ __global__ __launch_bounds__(kBalBlock) void k_slab_layer_count(DevConsts c, con
                                                                 int n_layers, int* __restrict__ counts) {
   __shared__ int hist[kBalMaxLayers];
   for (int k = threadIdx.x; k < n_layers; k += kBalBlock) hist[k] = 0;
-  bal_sync_lds();
+  lds_barrier();
   const int lane = threadIdx.x & (kWave - 1);
   const int n = live_n(c);
   // (the trip count is the same for every lane of a workgroup: ballot and shuffle see whole waves)
@@ -44,7 +36,7 @@ __global__ __launch_bounds__(kBalBlock) void k_slab_layer_count(DevConsts c, con
       atomicAdd(&hist[layer], next - lane);
     }
   }
-  bal_sync_lds();
+  lds_barrier();
   for (int k = threadIdx.x; k < n_layers; k += kBalBlock) {
     const int v = hist[k];
     if (v != 0) atomicAdd(&counts[k], v);

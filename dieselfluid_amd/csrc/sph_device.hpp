@@ -127,9 +127,27 @@ struct SkinGate {
   __device__ __forceinline__ bool closed() const { return st != nullptr && st->rebuild == 0; }
 };
 
+// __syncthreads() with the wave's own LDS traffic drained first, stated explicitly: the library's only barrier.  hipcc
+// leaves the `s_waitcnt lgkmcnt(0)` in front of an s_barrier to its waitcnt pass, and at the head of the tiled kernels'
+// double-buffered loops (LDS writes at the END of the loop body, the barrier at its HEAD, reached over the back edge) that
+// pass emitted none: the ISA had `ds_write_b128 ... s_branch ... s_barrier`.  A wave could then pass the barrier while a
+// sibling's last records or table words were still on their way, and one 16M run in three met a stale record within a few
+// thousand steps (densities off, then a blow-up): profiles/README.md, r03.  tools/isa_audit.py keeps every unit that way.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
 // ---------------------------------------------------------------------------------
 // scalar helpers
 // ---------------------------------------------------------------------------------
+// voxel i of a lattice axis (GridPosition in float32): one multiplication, one addition, each rounded, never fused
+__device__ __forceinline__ float lattice_coord(float o, float s, int i) { return __fadd_rn(o, __fmul_rn(s, (float)i)); }
+// the dot product in the one order the build-defined rules name (tests/sdf_ref.py)
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
 template <bool FAST>
 __device__ __forceinline__ float dsl_sqrt(float x) {
   if constexpr (FAST) return __builtin_amdgcn_sqrtf(x);

@@ -1,10 +1,10 @@
 // surface_device.hpp -- what the two fluid-surface units share on the device: surface.hip (the triangle soup) and
-// surface_mesh.hip (the indexed mesh).  The lattice, the brick of 8 x 8 x 4 cubes with its 9 x 9 x 5 staged voxels, the inside
-// mask of a cube, the prefix over a workgroup, and the barrier with its LDS drain.  Everything is __forceinline__ in an unnamed
+// surface_mesh.hip (the indexed mesh).  The lattice with its brick counts, the brick of 8 x 8 x 4 cubes with its 9 x 9 x 5 staged
+// voxels, the inside mask of a cube, and the prefix over a workgroup.  Everything is __forceinline__ in an unnamed
 // namespace: each unit gets its own copy, and no __global__ function lives here.
 #pragma once
 
-#include "sph_device.hpp"
+#include "lattice.hpp"
 #include "surface_table.hpp"
 
 namespace dsl {
@@ -19,22 +19,11 @@ static_assert(kSurfBX * kSurfBY * kSurfBZ == kSurfBlock && kSurfBX * kSurfBY == 
 
 typedef unsigned long long surf_u64;
 
-struct SurfLattice {
-  float o[3], s[3];
-  int n[3];
-  int nbx, nby;
+struct SurfLattice : Lattice {
+  int nbx, nby;  // bricks of 8 x 8 x 4 cubes along x and y
 };
 
 namespace {
-// the barrier with its LDS drain stated (as volume.hip's: tools/isa_audit.py keeps it that way)
-__device__ __forceinline__ void surf_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// dsl_field_volume's voxel coordinate: one multiplication, one addition, each rounded
-__device__ __forceinline__ float surf_coord(float o, float s, int i) { return __fadd_rn(o, __fmul_rn(s, (float)i)); }
-
 struct SurfBrick {
   int bi, bj, bk;
 };
@@ -58,7 +47,7 @@ __device__ __forceinline__ void surf_stage(const float* __restrict__ vol, const 
     if (vi < g.n[0] && vj < g.n[1] && vk < g.n[2]) v = vol[((size_t)vk * g.n[1] + vj) * g.n[0] + vi];
     s_v[e] = v;
   }
-  surf_sync_lds();
+  lds_barrier();
 }
 
 __device__ __forceinline__ int surf_corner_at(int base, int c) {
@@ -94,7 +83,7 @@ __device__ __forceinline__ T surf_block_scan(T v, T* s_wave, T& total) {
     if (lane >= off) incl += o;
   }
   if (lane == kWave - 1) s_wave[wave] = incl;
-  surf_sync_lds();
+  lds_barrier();
   T before = 0;
   total = 0;
 #pragma unroll

@@ -73,7 +73,7 @@ __device__ __forceinline__ void mesh_stage(const float* __restrict__ vol, const 
     if (vi >= 0 && vj >= 0 && vk >= 0 && vi < g.n[0] && vj < g.n[1] && vk < g.n[2]) v = vol[((size_t)vk * g.n[1] + vj) * g.n[0] + vi];
     s_v[e] = v;
   }
-  surf_sync_lds();
+  lds_barrier();
 }
 
 // one component of the volume's gradient at the voxel at e of the image, whose value is vp and whose index along the axis
@@ -82,7 +82,7 @@ __device__ __forceinline__ void mesh_stage(const float* __restrict__ vol, const 
 __device__ __forceinline__ float mesh_grad(const float* s_v, int e, int stride, float vp, float o, float s, int idx) {
   const float vm = s_v[e - stride], vq = s_v[e + stride];
   const bool um = mesh_finite(vm), uq = mesh_finite(vq);
-  const float xm = surf_coord(o, s, idx - 1), xp = surf_coord(o, s, idx), xq = surf_coord(o, s, idx + 1);
+  const float xm = lattice_coord(o, s, idx - 1), xp = lattice_coord(o, s, idx), xq = lattice_coord(o, s, idx + 1);
   const float hi = uq ? vq : vp, lo = um ? vm : vp;
   const float xhi = uq ? xq : xp, xlo = um ? xm : xp;
   return (um || uq) ? __fsub_rn(hi, lo) / __fsub_rn(xhi, xlo) : 0.0f;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kSurfBlock) void k_mesh_vertex_count(const float* _
     for (int c = 0; c < 8; ++c) finite = finite && mesh_finite(s_v[at + mesh_offset<kMeshCX, kMeshCY>(c)]);
     s_live[e] = finite ? 1 : 0;
   }
-  surf_sync_lds();
+  lds_barrier();
   const int tid = threadIdx.x;
   const int lx = tid & (kSurfBX - 1), ly = (tid / kSurfBX) & (kSurfBY - 1), lz = tid / (kSurfBX * kSurfBY);
   const int at = ((lz + 1) * kMeshCY + ly + 1) * kMeshCX + lx + 1;
@@ -158,8 +158,8 @@ __global__ __launch_bounds__(kSurfBlock) void k_mesh_vertex_emit(const float* __
   const surf_u64 first = brick_off + (surf_u64)(word >> 7);
   const int at = ((lz + 1) * kMeshSY + ly + 1) * kMeshSX + lx + 1;
   const float vu = s_v[at];
-  const float xu = surf_coord(g.o[0], g.s[0], vi), yu = surf_coord(g.o[1], g.s[1], vj), zu = surf_coord(g.o[2], g.s[2], vk);
-  const float x1 = surf_coord(g.o[0], g.s[0], vi + 1), y1 = surf_coord(g.o[1], g.s[1], vj + 1), z1 = surf_coord(g.o[2], g.s[2], vk + 1);
+  const float xu = lattice_coord(g.o[0], g.s[0], vi), yu = lattice_coord(g.o[1], g.s[1], vj), zu = lattice_coord(g.o[2], g.s[2], vk);
+  const float x1 = lattice_coord(g.o[0], g.s[0], vi + 1), y1 = lattice_coord(g.o[1], g.s[1], vj + 1), z1 = lattice_coord(g.o[2], g.s[2], vk + 1);
   float gux = 0.0f, guy = 0.0f, guz = 0.0f;
   if (nrm) {
     gux = mesh_grad(s_v, at, 1, vu, g.o[0], g.s[0], vi);
@@ -267,15 +267,6 @@ __global__ __launch_bounds__(kSurfBlock) void k_mesh_index_emit(const float* __r
 }
 
 namespace {
-
-// phase p of the last call: events 2 p and 2 p + 1
-void mesh_mark(dsl_handle* h, int k) {
-  if (h->timing != 1) return;
-  if (!h->mesh_ev[k]) (void)hipEventCreate(&h->mesh_ev[k]);
-  (void)hipEventRecord(h->mesh_ev[k], h->stream);
-  if (k & 1) h->mesh_timed |= 1 << (k >> 1);
-}
-
 MeshLattice mesh_lattice(const SurfLattice& g, long long* nvb) {
   MeshLattice m;
   m.g = g;
@@ -302,7 +293,7 @@ int mesh_count(dsl_handle* h, const float* vol, const SurfLattice& g, long long 
   if (!h->mesh_ctr) {
     if (int rc = dev_alloc(h, &h->mesh_ctr, 2)) return rc;
   }
-  h->mesh_timed = 0;
+  h->mesh_clock.reset();
   if (int rc = surf_count(h, vol, g, nb, iso, dev_counts ? dev_counts + 1 : nullptr)) return rc;
   if (nb == 0) {  // no cubes: no live cube, no vertex
     HIP_TRY(h, hipMemsetAsync(h->mesh_ctr, 0, 2 * sizeof(surf_u64), h->stream));
@@ -314,18 +305,18 @@ int mesh_count(dsl_handle* h, const float* vol, const SurfLattice& g, long long 
   std::vector<long long> len;
   std::vector<size_t> first;
   const size_t all = surf_scan_layout(nvb, &len, &first);
-  if (int rc = surf_reserve(h, &h->mesh_scan, &h->mesh_scan_count, all, "the vertex scan array")) return rc;
+  if (int rc = reserve(h, h->mesh_scan, all, "the vertex scan array")) return rc;
   const size_t nvox = (size_t)g.n[0] * g.n[1] * g.n[2];
-  if (int rc = surf_reserve(h, &h->mesh_words, &h->mesh_words_count, nvox, "the per-voxel vertex words")) return rc;
-  mesh_mark(h, 0);
+  if (int rc = reserve(h, h->mesh_words, nvox, "the per-voxel vertex words")) return rc;
+  h->mesh_clock.begin(h, 0);
   int rc = timed(h, DSL_K_SURFACE_MESH, [&] {
-    hipLaunchKernelGGL(k_mesh_vertex_count, dim3((unsigned)nvb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->mesh_words, h->mesh_scan);
+    hipLaunchKernelGGL(k_mesh_vertex_count, dim3((unsigned)nvb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->mesh_words.p, h->mesh_scan.p);
   });
   if (rc) return rc;
-  mesh_mark(h, 1);
-  mesh_mark(h, 2);
-  if ((rc = surf_scan_run(h, DSL_K_SURFACE_MESH, h->mesh_scan, len, first, h->mesh_ctr, dev_counts))) return rc;
-  mesh_mark(h, 3);
+  h->mesh_clock.end(h, 0);
+  h->mesh_clock.begin(h, 1);
+  if ((rc = surf_scan_run(h, DSL_K_SURFACE_MESH, h->mesh_scan.p, len, first, h->mesh_ctr, dev_counts))) return rc;
+  h->mesh_clock.end(h, 1);
   return DSL_OK;
 }
 
@@ -335,22 +326,22 @@ int mesh_emit(dsl_handle* h, const float* vol, const SurfLattice& g, long long n
   long long nvb = 0;
   const MeshLattice m = mesh_lattice(g, &nvb);
   if (cap_v > 0) {
-    mesh_mark(h, 4);
+    h->mesh_clock.begin(h, 2);
     const int rc = timed(h, DSL_K_SURFACE_MESH, [&] {
-      hipLaunchKernelGGL(k_mesh_vertex_emit, dim3((unsigned)nvb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->mesh_words, h->mesh_scan,
-                         h->mesh_ctr, pos, nrm, (surf_u64)cap_v);
+      hipLaunchKernelGGL(k_mesh_vertex_emit, dim3((unsigned)nvb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->mesh_words.p,
+                         h->mesh_scan.p, h->mesh_ctr, pos, nrm, (surf_u64)cap_v);
     });
     if (rc) return rc;
-    mesh_mark(h, 5);
+    h->mesh_clock.end(h, 2);
   }
   if (cap_t > 0) {
-    mesh_mark(h, 6);
+    h->mesh_clock.begin(h, 3);
     const int rc = timed(h, DSL_K_SURFACE_MESH, [&] {
-      hipLaunchKernelGGL(k_mesh_index_emit, dim3((unsigned)nb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->surf_scan, h->surf_ctr,
-                         h->mesh_words, h->mesh_scan, (int*)idx, (surf_u64)cap_t);
+      hipLaunchKernelGGL(k_mesh_index_emit, dim3((unsigned)nb), dim3(kSurfBlock), 0, h->stream, vol, m, iso, h->surf_scan.p, h->surf_ctr,
+                         h->mesh_words.p, h->mesh_scan.p, (int*)idx, (surf_u64)cap_t);
     });
     if (rc) return rc;
-    mesh_mark(h, 7);
+    h->mesh_clock.end(h, 3);
   }
   return DSL_OK;
 }
@@ -379,21 +370,16 @@ int surface_mesh_option(dsl_handle* h, int option, double* value) {
   }
   // the last call's launches by phase, from device events of their own (recorded while dsl_timing_enable(1) holds)
   const int p = option - DSL_OPT_SURFACE_MESH_VCOUNT_MS;
-  if (p < 0 || p > 3 || !((h->mesh_timed >> p) & 1)) return DSL_OK;
-  HIP_TRY(h, hipEventSynchronize(h->mesh_ev[2 * p + 1]));
-  float ms = 0.f;
-  HIP_TRY(h, hipEventElapsedTime(&ms, h->mesh_ev[2 * p], h->mesh_ev[2 * p + 1]));
-  *value = (double)ms;
-  return DSL_OK;
+  if (p < 0 || p > 3) return DSL_OK;
+  return h->mesh_clock.ms(h, p, value);
 }
 
 void surface_mesh_free(dsl_handle* h) {
-  (void)hipFree(h->mesh_words);
-  (void)hipFree(h->mesh_scan);
+  release(h->mesh_words);
+  release(h->mesh_scan);
   (void)hipFree(h->mesh_ctr);
-  (void)hipFree(h->mesh_stage);
-  for (hipEvent_t e : h->mesh_ev)
-    if (e) (void)hipEventDestroy(e);
+  release(h->mesh_stage);
+  h->mesh_clock.destroy();
 }
 
 }  // namespace dsl
@@ -443,7 +429,7 @@ int dsl_field_surface_indexed(dsl_handle* h, int scalar_buffer, const float orig
   SurfLattice g;
   long long nb = 0;
   if (int rc = surf_lattice(h, who, origin, step, dims, &g, &nb)) return rc;
-  if (int rc = mesh_count(h, h->vol_stage, g, nb, iso, nullptr)) return rc;
+  if (int rc = mesh_count(h, h->vol_stage.p, g, nb, iso, nullptr)) return rc;
   surf_u64 vt[2];
   if (int rc = mesh_read_counts(h, vt)) return rc;
   const size_t take_v = (size_t)std::min<surf_u64>(vt[0], (surf_u64)cap_vertices);
@@ -451,12 +437,11 @@ int dsl_field_surface_indexed(dsl_handle* h, int scalar_buffer, const float orig
   if (take_v + take_t > 0) {
     // positions, normals, then the index triples (32-bit words like the floats) in one array of the library's own
     static_assert(sizeof(int32_t) == sizeof(float), "one array holds both");
-    if (int rc = surf_reserve(h, &h->mesh_stage, &h->mesh_stage_count, 6 * take_v + 3 * take_t, "dsl_field_surface_indexed: the mesh array"))
-      return rc;
-    float* pos = h->mesh_stage;
-    float* nrm = host_normals ? h->mesh_stage + 3 * take_v : nullptr;
-    int32_t* idx = (int32_t*)(h->mesh_stage + 6 * take_v);
-    if (int rc = mesh_emit(h, h->vol_stage, g, nb, iso, pos, nrm, take_v, idx, take_t)) return rc;
+    if (int rc = reserve(h, h->mesh_stage, 6 * take_v + 3 * take_t, "dsl_field_surface_indexed: the mesh array")) return rc;
+    float* pos = h->mesh_stage.p;
+    float* nrm = host_normals ? pos + 3 * take_v : nullptr;
+    int32_t* idx = (int32_t*)(pos + 6 * take_v);
+    if (int rc = mesh_emit(h, h->vol_stage.p, g, nb, iso, pos, nrm, take_v, idx, take_t)) return rc;
     if (take_v > 0) {
       HIP_TRY(h, hipMemcpyAsync(host_positions, pos, 3 * take_v * sizeof(float), hipMemcpyDeviceToHost, h->stream));
       if (nrm) HIP_TRY(h, hipMemcpyAsync(host_normals, nrm, 3 * take_v * sizeof(float), hipMemcpyDeviceToHost, h->stream));

@@ -14,8 +14,6 @@
 #include "engine.hpp"
 #include "sph_device.hpp"
 
-#include <cmath>
-
 namespace dsl {
 
 constexpr int kVolBlock = 256;
@@ -29,21 +27,7 @@ constexpr int kVolMaxStarts = 1024;
 constexpr int kVolMaxRows = kWave;  // (the rows' prefix is one wave scan)
 constexpr int kVolCounters = 4;
 
-struct VolLattice {
-  float o[3], s[3];
-  int n[3];
-};
-
 namespace {
-// the barrier with its LDS drain stated (as kernels_tiled.hpp's: tools/isa_audit.py keeps it that way)
-__device__ __forceinline__ void vol_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// GridPosition in float32: one multiplication, one addition, each rounded (never fused, whatever the flags)
-__device__ __forceinline__ float vol_coord(float o, float s, int i) { return __fadd_rn(o, __fmul_rn(s, (float)i)); }
-
 // k_field_interpolate's sum at (x, y, z), candidates from global memory
 template <bool FAST>
 __device__ __forceinline__ float vol_sum_global(const DevConsts& c, const Neigh& nb, const CSoa3& p,
@@ -63,13 +47,13 @@ __device__ __forceinline__ float vol_sum_global(const DevConsts& c, const Neigh&
 
 template <bool FAST>
 __global__ __launch_bounds__(kVolBlock) void k_volume_sweep(DevConsts c, Neigh nb, CSoa3 p, const float* __restrict__ rho,
-                                                            int field, VolLattice g, int nvox, float* __restrict__ out) {
+                                                            int field, Lattice g, int nvox, float* __restrict__ out) {
   const int v = blockIdx.x * kVolBlock + threadIdx.x;  // (at most 2^30 voxels)
   if (v >= nvox) return;
   const int i = v % g.n[0], jk = v / g.n[0];
   const int j = jk % g.n[1], k = jk / g.n[1];
-  out[v] = vol_sum_global<FAST>(c, nb, p, rho, field, vol_coord(g.o[0], g.s[0], i), vol_coord(g.o[1], g.s[1], j),
-                                vol_coord(g.o[2], g.s[2], k));
+  out[v] = vol_sum_global<FAST>(c, nb, p, rho, field, lattice_coord(g.o[0], g.s[0], i), lattice_coord(g.o[1], g.s[1], j),
+                                lattice_coord(g.o[2], g.s[2], k));
 }
 
 // A lane's voxel in brick b: bricks x fastest; inside a brick 2 x 2 x 1 waves of 4 x 4 x 4 lanes (CUBES = true: the LDS
@@ -82,7 +66,7 @@ struct VolVoxel {
   size_t at;
 };
 template <bool CUBES>
-__device__ __forceinline__ VolVoxel vol_voxel(const VolLattice& g, int b, int nbx, int nby, int tid) {
+__device__ __forceinline__ VolVoxel vol_voxel(const Lattice& g, int b, int nbx, int nby, int tid) {
   const int lane = tid & (kWave - 1), wave = tid / kWave;
   VolVoxel v;
   v.bi = b % nbx;
@@ -93,9 +77,9 @@ __device__ __forceinline__ VolVoxel vol_voxel(const VolLattice& g, int b, int nb
   const int vj = v.bj * kVolBY + (CUBES ? (wave >> 1) * 4 + ((lane >> 2) & 3) : lane >> 3);
   const int vk = v.bk * kVolBZ + (CUBES ? lane >> 4 : wave);
   v.mine = vi < g.n[0] && vj < g.n[1] && vk < g.n[2];
-  v.x = vol_coord(g.o[0], g.s[0], vi);
-  v.y = vol_coord(g.o[1], g.s[1], vj);
-  v.z = vol_coord(g.o[2], g.s[2], vk);
+  v.x = lattice_coord(g.o[0], g.s[0], vi);
+  v.y = lattice_coord(g.o[1], g.s[1], vj);
+  v.z = lattice_coord(g.o[2], g.s[2], vk);
   v.at = ((size_t)vk * g.n[1] + vj) * g.n[0] + vi;
   return v;
 }
@@ -103,7 +87,7 @@ __device__ __forceinline__ VolVoxel vol_voxel(const VolLattice& g, int b, int nb
 // ctr[0] bricks swept out of LDS, [1] bricks whose image did not fit (global sweep), [2] bricks with no particle in reach,
 // [3] records the LDS bricks staged
 __global__ __launch_bounds__(kVolBlock) void k_volume_bricks(DevConsts c, const int* __restrict__ cell_start, CSoa3 p,
-                                                             const float* __restrict__ rho, int field, VolLattice g,
+                                                             const float* __restrict__ rho, int field, Lattice g,
                                                              int nbx, int nby, float* __restrict__ out,
                                                              unsigned long long* __restrict__ ctr) {
   __shared__ float4 s_rec[kVolCap];
@@ -126,8 +110,8 @@ __global__ __launch_bounds__(kVolBlock) void k_volume_bricks(DevConsts c, const 
   const int edge[3] = {kVolBX, kVolBY, kVolBZ};
   for (int a = 0; a < 3; ++a) {
     const int last = min(first[a] + edge[a], g.n[a]) - 1;
-    const int c0 = cell_coord(vol_coord(g.o[a], g.s[a], first[a]), c.gmin[a], c.inv_cell, c.dims[a]);
-    const int c1 = cell_coord(vol_coord(g.o[a], g.s[a], last), c.gmin[a], c.inv_cell, c.dims[a]);
+    const int c0 = cell_coord(lattice_coord(g.o[a], g.s[a], first[a]), c.gmin[a], c.inv_cell, c.dims[a]);
+    const int c1 = cell_coord(lattice_coord(g.o[a], g.s[a], last), c.gmin[a], c.inv_cell, c.dims[a]);
     lo[a] = max(c0 - 1, 0);
     hi[a] = min(c1 + 1, c.dims[a] - 1);
   }
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(kVolBlock) void k_volume_bricks(DevConsts c, const 
       const int ry = r % ncy, rz = r / ncy;
       s_start[e] = cell_start[((lo[2] + rz) * c.dims[1] + (lo[1] + ry)) * c.dims[0] + lo[0] + xo];
     }
-    vol_sync_lds();
+    lds_barrier();
     // where each row's records begin in the image: an exclusive prefix over the rows' lengths, one scan in every wave
     const int len = lane < nrows ? s_start[lane * row_len + ncx] - s_start[lane * row_len] : 0;
     int incl = len;
@@ -181,7 +165,7 @@ __global__ __launch_bounds__(kVolBlock) void k_volume_bricks(DevConsts c, const 
       s_f[base + q] = scalar_field<true>(c, field, rho, j);
     }
   }
-  vol_sync_lds();
+  lds_barrier();
   if (!mine) return;
 
   // the voxel's own 27 cells as 9 x-runs, z, y, then slots ascending: for_each_grid_candidate's order.  (The bounds are
@@ -236,19 +220,9 @@ int field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], const 
   if (h->c.n_ptr || h->c.slab_axis >= 0) return fail(h, DSL_ERR_UNSUPPORTED, "field operators are not available in slab mode");
   const int field = scalar_buffer == DSL_BUF_DENSITIES ? 0 : (scalar_buffer == DSL_BUF_PRESSURES ? 1 : -1);
   if (field < 0) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: scalar_buffer must be DSL_BUF_DENSITIES or DSL_BUF_PRESSURES");
-  if (!origin || !step || !dims) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: origin, step and dims must not be NULL");
-  VolLattice g;
-  long long nvox = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: every entry of dims must be >= 1");
-    nvox *= dims[a];  // (each factor < 2^31 and the running product is checked: no overflow)
-    if (nvox > (1ll << 30)) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: dims holds more than 2^30 voxels");
-    if (!(std::isfinite(step[a]) && step[a] > 0.0f)) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: every entry of step must be finite and > 0");
-    if (!std::isfinite(origin[a])) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: every entry of origin must be finite");
-    g.o[a] = origin[a];
-    g.s[a] = step[a];
-    g.n[a] = dims[a];
-  }
+  Lattice g;
+  long long nvox = 0;
+  if (int rc = lattice_check(h, "dsl_field_volume", origin, step, dims, 1, &g, &nvox)) return rc;
   if (!dev_out && !host_out && !to_stage) return fail(h, DSL_ERR_INVALID, "dsl_field_volume: dev_out and host_out are both NULL");
   if (h->skin_live)
     if (int rc = skin_settle(h)) return rc;
@@ -256,21 +230,8 @@ int field_volume(dsl_handle* h, int scalar_buffer, const float origin[3], const 
 
   float* out = dev_out;
   if (!out) {
-    if (h->vol_stage_count < (size_t)nvox) {
-      (void)hipFree(h->vol_stage);
-      h->dev_bytes -= h->vol_stage_count * sizeof(float);
-      h->vol_stage = nullptr;
-      h->vol_stage_count = 0;
-      const hipError_t e = hipMalloc((void**)&h->vol_stage, (size_t)nvox * sizeof(float));
-      if (e != hipSuccess) {
-        h->vol_stage = nullptr;
-        (void)hipGetLastError();  // (the handle stays usable: the next launch check must not meet this error)
-        return fail(h, DSL_ERR_NOMEM, std::string("dsl_field_volume: the staging array: hipMalloc: ") + hipGetErrorString(e));
-      }
-      h->vol_stage_count = (size_t)nvox;
-      h->dev_bytes += h->vol_stage_count * sizeof(float);
-    }
-    out = h->vol_stage;
+    if (int rc = reserve(h, h->vol_stage, (size_t)nvox, "dsl_field_volume: the staging array")) return rc;
+    out = h->vol_stage.p;
   }
 
   const bool fast = h->prm.math_mode == DSL_MATH_FAST;
