@@ -1023,3 +1023,127 @@ func (e *Engine) ColliderVolumeImpulse(reset bool) (impulse, torque [3]float32, 
 	err = e.ck(C.dsl_collider_volume_impulse(e.h, (*C.float)(unsafe.Pointer(&impulse[0])), (*C.float)(unsafe.Pointer(&torque[0])), C.int(r)))
 	return
 }
+
+// ---- rigid bodies: several volume colliders, their poses integrated on the device (include/dslsph.h: dsl_body_add) ----
+
+const (
+	// the most bodies a handle takes
+	MaxBodies = int(C.DSL_MAX_BODIES)
+	// the number of bodies (get); 1: the step drivers integrate the poses (set/get, default 1)
+	OptBodies          = int(C.DSL_OPT_BODIES)
+	OptBodiesIntegrate = int(C.DSL_OPT_BODIES_INTEGRATE)
+)
+
+// BodyProps: the inverse mass, the inverse principal moments about the axes of the body's frame, a constant acceleration
+// (gravity), and the collider's radius and restitution.  InvMass, InvInertia and Accel all zero: a kinematic body.
+type BodyProps struct {
+	InvMass     float32
+	InvInertia  [3]float32
+	Accel       [3]float32
+	Radius      float32
+	Restitution float32
+}
+
+// BodyState: the orientation Quat (w, x, y, z), the body frame's origin Trans in world coordinates (the point torques
+// refer to: the centre of mass), its velocity LinVel and the angular velocity AngVel, world.
+type BodyState struct {
+	Quat   [4]float32
+	Trans  [3]float32
+	LinVel [3]float32
+	AngVel [3]float32
+}
+
+// BodyAtRest: the identity, at rest
+func BodyAtRest() BodyState {
+	return BodyState{Quat: [4]float32{1, 0, 0, 0}}
+}
+
+func (p *BodyProps) c() C.dsl_body_props {
+	var out C.dsl_body_props
+	out.inv_mass = C.float(p.InvMass)
+	for a := 0; a < 3; a++ {
+		out.inv_inertia[a] = C.float(p.InvInertia[a])
+		out.accel[a] = C.float(p.Accel[a])
+	}
+	out.radius = C.float(p.Radius)
+	out.restitution = C.float(p.Restitution)
+	return out
+}
+
+func (s *BodyState) c() C.dsl_body_state {
+	var out C.dsl_body_state
+	for a := 0; a < 4; a++ {
+		out.quat[a] = C.float(s.Quat[a])
+	}
+	for a := 0; a < 3; a++ {
+		out.trans[a] = C.float(s.Trans[a])
+		out.lin_vel[a] = C.float(s.LinVel[a])
+		out.ang_vel[a] = C.float(s.AngVel[a])
+	}
+	return out
+}
+
+// AddBody: a rigid body from a distance volume -- devVolume (device memory) or hostVolume, exactly one of them; the
+// library keeps a copy.  Bodies get the ids 0, 1, ... in the order they were added, which is the order the pass applies
+// them in.  It excludes a collider mesh and the single volume collider.
+func (e *Engine) AddBody(devVolume unsafe.Pointer, hostVolume []float32, origin, step [3]float32, dims [3]int32, props BodyProps, state BodyState) (id int, err error) {
+	var hp *C.float
+	if len(hostVolume) > 0 {
+		if len(hostVolume) < int(dims[0])*int(dims[1])*int(dims[2]) {
+			return -1, errors.New("AddBody: hostVolume is shorter than the lattice")
+		}
+		hp = (*C.float)(unsafe.Pointer(&hostVolume[0]))
+	}
+	cp, cs := props.c(), state.c()
+	var cid C.int
+	err = e.ck(C.dsl_body_add(e.h, (*C.float)(devVolume), hp, (*C.float)(unsafe.Pointer(&origin[0])), (*C.float)(unsafe.Pointer(&step[0])), (*C.int32_t)(unsafe.Pointer(&dims[0])), &cp, &cs, &cid))
+	return int(cid), err
+}
+
+// ClearBodies: removes every body (there is no removal of one: the order is part of the rule)
+func (e *Engine) ClearBodies() error {
+	return e.ck(C.dsl_bodies_clear(e.h))
+}
+
+// SetBodyState, SetBodyProps: between steps; they hold from the next pass on
+func (e *Engine) SetBodyState(body int, state BodyState) error {
+	cs := state.c()
+	return e.ck(C.dsl_body_set_state(e.h, C.int(body), &cs))
+}
+
+func (e *Engine) SetBodyProps(body int, props BodyProps) error {
+	cp := props.c()
+	return e.ck(C.dsl_body_set_props(e.h, C.int(body), &cp))
+}
+
+// BodyState: the state the device holds and what the fluid handed to the body since the last reset -- the impulse and
+// the torque impulse about Trans (blocking); reset zeroes the accumulators after the read.
+func (e *Engine) BodyState(body int, reset bool) (state BodyState, impulse, torque [3]float32, err error) {
+	r := 0
+	if reset {
+		r = 1
+	}
+	var cs C.dsl_body_state
+	err = e.ck(C.dsl_body_get_state(e.h, C.int(body), &cs, (*C.float)(unsafe.Pointer(&impulse[0])), (*C.float)(unsafe.Pointer(&torque[0])), C.int(r)))
+	for a := 0; a < 4; a++ {
+		state.Quat[a] = float32(cs.quat[a])
+	}
+	for a := 0; a < 3; a++ {
+		state.Trans[a] = float32(cs.trans[a])
+		state.LinVel[a] = float32(cs.lin_vel[a])
+		state.AngVel[a] = float32(cs.ang_vel[a])
+	}
+	return
+}
+
+// BodyQuery: the interpolated distance (N) and the world-space unit gradient (3 N) of one body at its current pose, at
+// every fluid particle in host order, no response (blocking).
+func (e *Engine) BodyQuery(body int) (dist, normal []float32, err error) {
+	n := int(e.Params.n_particles)
+	dist, normal = make([]float32, n), make([]float32, 3*n)
+	if n == 0 {
+		return
+	}
+	err = e.ck(C.dsl_body_query(e.h, C.int(body), (*C.float)(unsafe.Pointer(&dist[0])), (*C.float)(unsafe.Pointer(&normal[0]))))
+	return
+}

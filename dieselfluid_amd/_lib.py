@@ -65,6 +65,17 @@ class Stats(C.Structure):
     ]
 
 
+class BodyProps(C.Structure):
+    """dsl_body_props (include/dslsph.h)."""
+    _fields_ = [("inv_mass", C.c_float), ("inv_inertia", C.c_float * 3), ("accel", C.c_float * 3), ("radius", C.c_float),
+                ("restitution", C.c_float)]
+
+
+class BodyState(C.Structure):
+    """dsl_body_state (include/dslsph.h): quat is (w, x, y, z)."""
+    _fields_ = [("quat", C.c_float * 4), ("trans", C.c_float * 3), ("lin_vel", C.c_float * 3), ("ang_vel", C.c_float * 3)]
+
+
 # dsl_transport (include/dslsph.h): the host's own transport behind dsl_comm_create_custom
 TR_GROUP = C.CFUNCTYPE(C.c_int, C.c_void_p)
 TR_XFER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -121,6 +132,12 @@ EXPORTS = {
     "dsl_collider_volume_query": (C.c_int, [_vp, _fp, _fp]),
     "dsl_collider_volume_motion": (C.c_int, [_vp, _fp, _fp, _fp, _fp]),
     "dsl_collider_volume_impulse": (C.c_int, [_vp, _fp, _fp, C.c_int]),
+    "dsl_body_add": (C.c_int, [_vp, _vp, _fp, _fp, _fp, _ip, C.POINTER(BodyProps), C.POINTER(BodyState), C.POINTER(C.c_int)]),
+    "dsl_bodies_clear": (C.c_int, [_vp]),
+    "dsl_body_set_state": (C.c_int, [_vp, C.c_int, C.POINTER(BodyState)]),
+    "dsl_body_set_props": (C.c_int, [_vp, C.c_int, C.POINTER(BodyProps)]),
+    "dsl_body_get_state": (C.c_int, [_vp, C.c_int, C.POINTER(BodyState), _fp, _fp, C.c_int]),
+    "dsl_body_query": (C.c_int, [_vp, C.c_int, _fp, _fp]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

@@ -266,7 +266,8 @@ int collide_pass_slab(dsl_handle* h) {
 }  // namespace
 
 namespace dsl {
-int collide_pass(dsl_handle* h) {
+int collide_pass(dsl_handle* h, bool step) {
+  if (h->n_bodies > 0) return bodies_pass(h, step && h->bodies_integrate);  // (rigid bodies exclude a volume and a mesh: bodies.hip)
   if (h->colv_on) return collide_volume_pass(h);  // (a volume collider excludes a mesh: sdf.hip)
   if (h->col_tri == 0) return DSL_OK;
   if (h->c.n_ptr) return collide_pass_slab(h);
@@ -296,6 +297,9 @@ int dsl_collider_set_mesh(dsl_handle* h, const float* vertices, const float* nor
     col_index_free(h);
     return DSL_OK;
   }
+  if (h->n_bodies > 0)
+    return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: rigid bodies exist, and a mesh collider, a volume collider and rigid bodies "
+                                    "exclude each other; remove the bodies first (dsl_bodies_clear)");
   if (h->colv_on)
     return fail(h, DSL_ERR_INVALID, "dsl_collider_set_mesh: a volume collider is set, and a mesh collider and a volume collider exclude "
                                     "each other; remove the volume first (dsl_collider_set_volume with dims = NULL)");

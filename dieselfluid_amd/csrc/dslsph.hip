@@ -1460,7 +1460,7 @@ constexpr int kSkinRetry = 2048;
 
 bool skin_usable(const dsl_handle* h) {
   return h->skin > 0.0f && h->steps >= h->skin_retry_at && h->prm.math_mode == DSL_MATH_FAST && !h->lsh && h->c.slab_axis < 0 && !h->c.n_ptr && h->nb == 0 &&
-         h->col_tri == 0 && !h->colv_on &&  // (the collide pass moves particles behind the kernel that measures displacement)
+         h->col_tri == 0 && !h->colv_on && h->n_bodies == 0 &&  // (the collide pass moves particles behind the kernel that measures displacement)
          !h->pci_active && h->c.xsph_eps == 0.0f && h->c.st_kappa == 0.0f && use_tiled(h) && h->nmask != nullptr &&
          (h->c.wcsph_pressure_force != 0 || h->c.wcsph_viscosity != 0);
 }
@@ -1640,7 +1640,7 @@ int dsl_wcsph_step(dsl_handle* h, int nsteps) {
     if (int rc = build_grid(h, false)) return rc;  // NN(): geometric neighbour rule -> every step
     if (int rc = density_pass(h)) return rc;        // DensityAll   wcsph.go:18
     if (int rc = force_integrate(h)) return rc;     // ExternalAll, PressureAll, Update wcsph.go:19-21
-    if (int rc = collide_pass(h)) return rc;        // (only while a collider mesh or volume is set)
+    if (int rc = collide_pass(h, true)) return rc;  // (only while a collider mesh, a volume or rigid bodies are set)
     h->steps++;
   }
   return DSL_OK;
@@ -1699,6 +1699,7 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
       return DSL_OK;
     case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
     case DSL_OPT_VOLUME_BRICKS: h->vol_bricks = value != 0.0; return DSL_OK;
+    case DSL_OPT_BODIES_INTEGRATE: h->bodies_integrate = value != 0.0; return DSL_OK;
     case DSL_OPT_COLLIDE_SLAB:
       if (value == 0.0 && h->col_slab && h->c.n_ptr && h->col_tri > 0)
         return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_SLAB cannot go back to 0 while a slab handle holds a "
@@ -1789,6 +1790,8 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
       return DSL_OK;
     }
     case DSL_OPT_VOLUME_BRICKS: *value = h->vol_bricks ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_BODIES: *value = (double)h->n_bodies; return DSL_OK;
+    case DSL_OPT_BODIES_INTEGRATE: *value = h->bodies_integrate ? 1.0 : 0.0; return DSL_OK;
     case DSL_OPT_VOLUME_LDS_BRICKS: return volume_brick_count(h, 0, value);  // (blocking: the kernel counts on the device)
     case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
     case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);
@@ -2039,7 +2042,7 @@ int pci_check(dsl_handle* h) {                   // :95-98
 
 int pci_end_step(dsl_handle* h) {                // Update :101 (positions advect with v + XSPH)
   if (int rc = update_pass(h, pci_extra_terms(h))) return rc;
-  if (int rc = collide_pass(h)) return rc;  // (only while a collider mesh or volume is set)
+  if (int rc = collide_pass(h, true)) return rc;  // (only while a collider mesh, a volume or rigid bodies are set)
   h->steps++;
   h->pci_steps++;
   return DSL_OK;
@@ -2114,6 +2117,7 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (axis >= 0 && h->nb > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: boundary particles are not supported in slab mode");
   if (axis >= 0 && h->col_tri > 0 && !h->col_slab) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
   if (axis >= 0 && h->colv_on) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a volume collider is not supported in slab mode");
+  if (axis >= 0 && h->n_bodies > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: rigid bodies are not supported in slab mode");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;

@@ -10,7 +10,8 @@
 //   surface_mesh.hip   the indexed mesh: dsl_surface_extract_indexed, dsl_field_surface_indexed and their three kernels
 //   sdf.hip            implicit colliders: dsl_mesh_distance_volume, dsl_collider_set_volume, the volume collide pass, their kernels
 //   sdf_rigid.hip      the volume collider in rigid motion: dsl_collider_volume_motion, dsl_collider_volume_impulse, their two kernels
-// The last five are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
+//   bodies.hip         rigid bodies: dsl_body_*, several volume colliders in one pass, the fold that integrates their poses
+// The last six are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
 // PhaseClock members): the lattice and its one check, the collider's cell evaluation, the arrays that grow on demand and the
 // per-phase event clocks.  The barrier with its LDS drain, the voxel coordinate and the ordered dot product are sph_device.hpp's.
 #pragma once
@@ -229,6 +230,16 @@ struct dsl_handle {
   float colv_trans[3] = {}, colv_lin[3] = {}, colv_ang[3] = {};
   dsl::DevArray<float> colv_partial;
   float* colv_acc = nullptr;
+  // rigid bodies (bodies.hip; dsl_body_add): n_bodies = 0: none, nothing is launched.  body_rec: DSL_MAX_BODIES records in
+  // device memory (volume pointer, lattice, props, state, R, accumulators), written by the host calls and by the fold's
+  // integration; body_vol: the library's copies of the volumes; body_partial: six sums per workgroup and body of the last
+  // pass, [body][component][workgroup]; body_query: dsl_body_query's staging (4 words per particle)
+  int n_bodies = 0;
+  bool bodies_integrate = true;  // DSL_OPT_BODIES_INTEGRATE
+  dsl::DevArray<unsigned char> body_rec;
+  dsl::DevArray<float> body_vol[DSL_MAX_BODIES];
+  dsl::DevArray<float> body_partial;
+  float* body_query = nullptr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -342,7 +353,8 @@ int slab_append_shifted(dsl_handle* h, const float* dev_message_a, const float* 
 // ---- defined in collider_host.hip ----
 void col_index_free(dsl_handle* h);
 int col_index_update(dsl_handle* h, bool on, float edge_req);
-int collide_pass(dsl_handle* h);
+// step: called by a step driver -- the rigid bodies' poses are integrated behind the pass (DSL_OPT_BODIES_INTEGRATE)
+int collide_pass(dsl_handle* h, bool step = false);
 
 // ---- defined in volume.hip ----
 int volume_brick_count(dsl_handle* h, int which, double* value);  // DSL_OPT_VOLUME_LDS_BRICKS (0), _FALLBACK_BRICKS, _EMPTY_BRICKS, _STAGED_RECORDS (3)
@@ -379,5 +391,9 @@ void sdf_rigid_free(dsl_handle* h);
 int collide_volume_rigid_reset(dsl_handle* h);  // motion off, the accumulators at zero (dsl_collider_set_volume)
 int collide_volume_rigid_pass(dsl_handle* h);   // the collide pass while a motion is set: the rigid pass and the fold
 int collide_volume_rigid_query(dsl_handle* h, float* qd, float* qn);  // dsl_collider_volume_query's launch at the pose in force
+
+// ---- defined in bodies.hip ----
+void bodies_free(dsl_handle* h);
+int bodies_pass(dsl_handle* h, bool integrate);  // the collide pass while bodies exist: the pass, the fold, the integration
 
 }  // namespace dsl

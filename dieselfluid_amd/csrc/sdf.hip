@@ -394,6 +394,7 @@ void sdf_free(dsl_handle* h) {
   release(h->colv_vol);
   (void)hipFree(h->colv_query);
   sdf_rigid_free(h);
+  bodies_free(h);
   h->sdf_clock.destroy();
 }
 
@@ -512,6 +513,9 @@ int dsl_collider_set_volume(dsl_handle* h, const float* dev_volume, const float*
     h->colv_on = false;
     return collide_volume_rigid_reset(h);
   }
+  if (h->n_bodies > 0)
+    return fail(h, DSL_ERR_INVALID, w + ": rigid bodies exist, and a mesh collider, a volume collider and rigid bodies exclude each "
+                                        "other; remove the bodies first (dsl_bodies_clear)");
   if (h->col_tri > 0)
     return fail(h, DSL_ERR_INVALID, w + ": a mesh collider is set, and a mesh collider and a volume collider exclude each other; "
                                         "remove the mesh first (dsl_collider_set_mesh with n_triangles = 0)");

@@ -17,7 +17,7 @@
 
 namespace dsl {
 
-constexpr int kRigidBlock = 256;
+// (kRigidBlock and the workgroup tree rigid_tree: lattice.hpp, shared with bodies.hip)
 
 // the lattice and the response's constants, then the motion: all by value, wave-uniform
 struct RigidVol {
@@ -26,30 +26,6 @@ struct RigidVol {
   float radius, rest, mass;
   float rot[9], trans[3], lin[3], ang[3];
 };
-
-namespace {
-// The tree of include/dslsph.h over the workgroup's 256 values per component: for off in 128, 64, ..., 1: c[l] += c[l + off]
-// for l < off.  Offsets 128 and 64 through LDS -- lane l < 64 forms (c[l] + c[l + 128]) + (c[l + 64] + c[l + 192]), which is
-// what the two steps leave in c[l] -- the rest by __shfl_down inside wave 0, whose lane 0 ends with the sums.
-__device__ __forceinline__ void rigid_tree(float (&c)[6], float* lds) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) lds[k * kRigidBlock + tid] = c[k];
-  lds_barrier();
-  if (tid < kWave) {  // (wave-uniform)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const float* q = lds + k * kRigidBlock + tid;
-      c[k] = (q[0] + q[128]) + (q[64] + q[192]);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) c[k] = c[k] + __shfl_down(c[k], off);
-    }
-  }
-}
-}  // namespace
 
 template <bool RESPOND>
 __global__ __launch_bounds__(kRigidBlock) void k_collide_volume_rigid(int n, int nb, Bnd bnd, RigidVol m, Soa3 p, Soa3 v,

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import DslError, Params, Stats, load_library
+from ._lib import BodyProps, BodyState, DslError, Params, Stats, load_library
 
 BUF = {
     "positions": 0, "velocities": 1, "forces": 2, "densities": 3, "pressures": 4,
@@ -566,6 +566,64 @@ class SPHEngine:
         self._ck(self._L.dsl_collider_volume_impulse(self._h, _fp(imp), _fp(trq), 1 if reset else 0))
         return imp, trq
 
+    # -- rigid bodies (include/dslsph.h: dsl_body_add) ------------------------------
+    @staticmethod
+    def _body_props(inv_mass=0.0, inv_inertia=(0.0, 0.0, 0.0), accel=(0.0, 0.0, 0.0), radius=0.0, restitution=0.0):
+        return BodyProps(inv_mass, (C.c_float * 3)(*inv_inertia), (C.c_float * 3)(*accel), radius, restitution)
+
+    @staticmethod
+    def _body_state(quat=(1.0, 0.0, 0.0, 0.0), trans=(0.0, 0.0, 0.0), lin_vel=(0.0, 0.0, 0.0), ang_vel=(0.0, 0.0, 0.0)):
+        return BodyState((C.c_float * 4)(*quat), (C.c_float * 3)(*trans), (C.c_float * 3)(*lin_vel), (C.c_float * 3)(*ang_vel))
+
+    def add_body(self, volume, origin, step, props: dict, state: dict | None = None, dims=None, dev_volume=None) -> int:
+        """A rigid body from a distance volume (`volume` of shape (nz, ny, nx), or `dev_volume` a device pointer with `dims`);
+        `props`: inv_mass, inv_inertia, accel, radius, restitution; `state`: quat (w, x, y, z), trans, lin_vel, ang_vel, None
+        being the identity at rest.  Returns the body's id: 0, 1, ... in the order of the calls."""
+        vol = None
+        if volume is not None:
+            vol = np.ascontiguousarray(volume, dtype=np.float32)
+            if vol.ndim != 3:
+                raise DslError("add_body: volume has the shape (nz, ny, nx)")
+            dims = vol.shape[::-1]
+        o, s, d = self._lattice(origin, step, dims)
+        pr = self._body_props(**props)
+        st = self._body_state(**state) if state is not None else None
+        bid = C.c_int(-1)
+        self._ck(self._L.dsl_body_add(self._h, C.c_void_p(dev_volume) if vol is None else None, _fp(vol) if vol is not None else None,
+                                      _fp(o), _fp(s), d.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(pr),
+                                      C.byref(st) if st is not None else None, C.byref(bid)))
+        return int(bid.value)
+
+    def clear_bodies(self):
+        self._ck(self._L.dsl_bodies_clear(self._h))
+
+    def set_body_state(self, body: int, **state):
+        """quat, trans, lin_vel, ang_vel of one body (what is left out: the identity / zero); holds from the next pass on"""
+        st = self._body_state(**state)
+        self._ck(self._L.dsl_body_set_state(self._h, body, C.byref(st)))
+
+    def set_body_props(self, body: int, **props):
+        pr = self._body_props(**props)
+        self._ck(self._L.dsl_body_set_props(self._h, body, C.byref(pr)))
+
+    def body_state(self, body: int, reset: bool = False):
+        """(state: dict of float32 arrays quat, trans, lin_vel, ang_vel; impulse (3,); torque impulse about trans (3,)) of one
+        body; `reset` zeroes its accumulators after the read"""
+        st = BodyState()
+        imp = np.zeros(3, dtype=np.float32)
+        trq = np.zeros(3, dtype=np.float32)
+        self._ck(self._L.dsl_body_get_state(self._h, body, C.byref(st), _fp(imp), _fp(trq), 1 if reset else 0))
+        state = {k: np.array(getattr(st, k)[:], dtype=np.float32) for k in ("quat", "trans", "lin_vel", "ang_vel")}
+        return state, imp, trq
+
+    def body_query(self, body: int):
+        """the interpolated distance and the world-space unit gradient of one body at every fluid particle, host order, no response"""
+        n = self.n_fluid
+        dist = np.empty(n, dtype=np.float32)
+        nrm = np.empty((n, 3), dtype=np.float32)
+        self._ck(self._L.dsl_body_query(self._h, body, _fp(dist), _fp(nrm)))
+        return dist, nrm
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -722,7 +780,7 @@ class SPHEngine:
                "surface_emit_ms": 60, "surface_vertices": 61, "surface_mesh_vcount_ms": 62, "surface_mesh_vscan_ms": 63,
                "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65,
                "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76,
-               "collider_volume_moving": 77}
+               "collider_volume_moving": 77, "bodies": 78, "bodies_integrate": 79}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

@@ -406,6 +406,82 @@ class SPH {
     ck(dsl_collider_volume_query(h_, dist ? dist->data() : nullptr, normal ? normal->data() : nullptr));
   }
 
+  // Rigid bodies: sph.Init's collider list (fluid.go:28,41) for distance volumes -- several VolumeColliders, each with a pose
+  // and velocities of its own, applied in list order, their poses integrated on the device from what the fluid hands to them
+  // (include/dslsph.h: dsl_body_add).  A Body's voxels stay in its own frame; State.Origin is the frame's origin in world
+  // coordinates, the point torques refer to (put it at the centre of mass).  InvMass = 0, InvInertia = 0, Accel = 0: a
+  // kinematic body.  Bodies exclude Colliders and Collider.
+  struct Body {
+    DistanceVolume Volume;
+    float Radius = 0.f, Restitution = 0.f;
+    float InvMass = 0.f, InvInertia[3] = {0.f, 0.f, 0.f}, Accel[3] = {0.f, 0.f, 0.f};
+    struct State {
+      float Quat[4] = {1.f, 0.f, 0.f, 0.f};  // w, x, y, z
+      float Origin[3] = {0.f, 0.f, 0.f}, LinVel[3] = {0.f, 0.f, 0.f}, AngVel[3] = {0.f, 0.f, 0.f};
+    } Pose;
+    dsl_body_props props() const {
+      dsl_body_props p{};
+      p.inv_mass = InvMass, p.radius = Radius, p.restitution = Restitution;
+      for (int a = 0; a < 3; ++a) p.inv_inertia[a] = InvInertia[a], p.accel[a] = Accel[a];
+      return p;
+    }
+  };
+  static dsl_body_state body_state(const Body::State& s) {
+    dsl_body_state out{};
+    for (int a = 0; a < 4; ++a) out.quat[a] = s.Quat[a];
+    for (int a = 0; a < 3; ++a) out.trans[a] = s.Origin[a], out.lin_vel[a] = s.LinVel[a], out.ang_vel[a] = s.AngVel[a];
+    return out;
+  }
+  // what Bodies::Get returns: the state the device holds and what the fluid handed to the body since the last reset
+  struct BodyReading {
+    Body::State Pose;
+    VolumeCollider::Momentum Momentum;
+  };
+  // The list itself, bound to the solver: ids are list positions.  There is no removal of one body (the order is part of the rule).
+  struct Bodies {
+    explicit Bodies(SPH& s) : s_(s) {}
+    int Add(const Body& b) {
+      const dsl_body_props p = b.props();
+      const dsl_body_state st = body_state(b.Pose);
+      int id = -1;
+      s_.ck(dsl_body_add(s_.h_, nullptr, b.Volume.Values.data(), b.Volume.origin, b.Volume.step, b.Volume.dims, &p, &st, &id));
+      return id;
+    }
+    void Clear() { s_.ck(dsl_bodies_clear(s_.h_)); }
+    int Count() {
+      double v = 0.0;
+      s_.ck(dsl_get_option(s_.h_, DSL_OPT_BODIES, &v));
+      return (int)v;
+    }
+    void Update(int id, const Body::State& pose) {
+      const dsl_body_state st = body_state(pose);
+      s_.ck(dsl_body_set_state(s_.h_, id, &st));
+    }
+    void UpdateProps(int id, const Body& b) {
+      const dsl_body_props p = b.props();
+      s_.ck(dsl_body_set_props(s_.h_, id, &p));
+    }
+    BodyReading Get(int id, bool reset = false) {
+      dsl_body_state st{};
+      BodyReading r;
+      s_.ck(dsl_body_get_state(s_.h_, id, &st, r.Momentum.Impulse, r.Momentum.Torque, reset ? 1 : 0));
+      for (int a = 0; a < 4; ++a) r.Pose.Quat[a] = st.quat[a];
+      for (int a = 0; a < 3; ++a) r.Pose.Origin[a] = st.trans[a], r.Pose.LinVel[a] = st.lin_vel[a], r.Pose.AngVel[a] = st.ang_vel[a];
+      return r;
+    }
+    // false: the step drivers leave the poses alone and the host scripts all motion (DSL_OPT_BODIES_INTEGRATE)
+    void Integrate(bool on) { s_.ck(dsl_set_option(s_.h_, DSL_OPT_BODIES_INTEGRATE, on ? 1.0 : 0.0)); }
+    void Distances(int id, std::vector<float>* dist, std::vector<float>* normal) {
+      if (dist) dist->resize((size_t)s_.particles_);
+      if (normal) normal->resize(3 * (size_t)s_.particles_);
+      s_.ck(dsl_body_query(s_.h_, id, dist ? dist->data() : nullptr, normal ? normal->data() : nullptr));
+    }
+
+   private:
+    SPH& s_;
+  };
+  Bodies RigidBodies() { return Bodies(*this); }
+
   // The fluid's surface as a mesh.Mesh (README.MD:38 "SPH/Fluid Surfaces"; the reference's renderer draws meshes): the
   // iso-surface of SPHField.Interpolate on the lattice origin + step * (i, j, k), evaluated, triangulated and wound on the
   // device (include/dslsph.h: dsl_field_surface).  density = false: the pressure field.  The buffer is sized from a guess --

@@ -575,6 +575,82 @@ int dsl_collider_volume_motion(dsl_handle *h, const float rot[9], const float tr
                                const float lin_vel[3], const float ang_vel[3]);
 int dsl_collider_volume_impulse(dsl_handle *h, float impulse[3], float torque[3], int reset);
 
+/* Rigid bodies: up to DSL_MAX_BODIES volume colliders, each with a pose of its own, and the poses integrated on the device
+ * (csrc/bodies.hip; tests/bodies_ref.py restates the rule operation for operation).  The reference's
+ * sph.Init(scl, origin, colliders []geom.Collider, ...) takes a list of colliders; this is that list for distance volumes.
+ *
+ * dsl_body_add: a body from a distance volume (exactly one of dev_volume / host_volume; the library copies it; the lattice
+ * is checked as dsl_collider_set_volume checks it, dims >= 2), its properties and its first state (NULL: the identity, at
+ * rest).  Bodies get the ids 0, 1, ... in the order they were added (*body_id, may be NULL).  Blocking.  There is no removal
+ * of one body, because the order is part of the rule; dsl_bodies_clear removes all of them (blocking).  Without bodies
+ * there is no launch and no bit changes.  The copies, the body records, the partial sums and the accumulators are the
+ * library's own: counted in DSL_OPT_DEVICE_BYTES, freed by dsl_bodies_clear and dsl_destroy.
+ *   dsl_body_props: inv_mass and inv_inertia (the inverse principal moments, about the axes of the body's frame) turn what
+ *   the fluid hands over into velocity; accel is a constant acceleration (gravity); radius and restitution are the
+ *   collider's.  inv_mass = 0, inv_inertia = 0 and accel = 0: a kinematic body, which moves with its velocities and ignores
+ *   the fluid.
+ *   dsl_body_state: quat (w, x, y, z) is the orientation, trans the body frame's origin in world coordinates -- the point
+ *   torques refer to, so a caller puts it at the centre of mass -- lin_vel the velocity of that point, ang_vel the
+ *   angular velocity, world.  The voxels stay in the body's frame.
+ * dsl_body_set_state / dsl_body_set_props replace one of the two between steps and take effect at the next pass (blocking);
+ * dsl_body_get_state reads the state and what the fluid handed to the body since the last reset (impulse, torque impulse
+ * about trans; any of the three pointers may be NULL; reset = 1 zeroes the accumulators after the read); blocking.
+ * dsl_body_query: d and the world-space n of every fluid particle in host order against one body at its current pose, no
+ * response, as dsl_collider_volume_query; blocking.
+ *   DSL_ERR_INVALID (dsl_last_error names the argument), before anything is touched, a refused call changes nothing: a
+ *   seventeenth body, a bad lattice or bad pointers, a non-finite entry anywhere, inv_mass, an inv_inertia entry or radius
+ *   < 0, a quaternion whose squared length is not > 0 (or not finite), an unknown body id; dsl_body_add while a mesh
+ *   collider or the single volume collider is set -- and dsl_collider_set_mesh / dsl_collider_set_volume while bodies
+ *   exist: the three kinds of collider exclude each other, and the message says what to remove first.
+ *   DSL_ERR_UNSUPPORTED: a slab handle; dsl_slab_config refuses while bodies exist.  The skin step is not taken while
+ *   bodies exist.  dsl_stats.max_vel / max_f, boundary particles and the PCISPH predictor state are not touched.
+ *   Rule.  float32, every operation rounded once, nothing fused, a dot product is (a.x b.x + a.y b.y) + a.z b.z, divisions
+ *   and square roots correctly rounded, the same in both math modes.
+ *   Pose.  dsl_body_set_state (and dsl_body_add) store q / |q|, |q| = sqrt(((w w + x x) + y y) + z z), each component
+ *   divided, and derive the row-major R = [1 - 2 (yy + zz), 2 (xy - wz), 2 (xz + wy);  2 (xy + wz), 1 - 2 (xx + zz),
+ *   2 (yz - wx);  2 (xz - wy), 2 (yz + wx), 1 - 2 (xx + yy)], every product, sum and difference rounded, each parenthesis
+ *   formed first.
+ *   Pass.  For every live fluid slot, in dsl_download_ids order, body 0, then 1, ..., then K - 1, in that order: the rule of
+ *   dsl_collider_volume_motion above (q, xl = R^T q, cell, d, g, n = R nl, push-out, u, vn, f, J = (mass f) n, tau = q x J)
+ *   with that body's radius, restitution, R, trans, lin_vel and ang_vel, applied to the particle's current x and v: body 1
+ *   sees what body 0 left.  A body's contribution from a slot is J, tau, or six +0.  Per body the workgroup partials (256
+ *   slots, the same tree) and the pass total are those of dsl_collider_volume_motion; then acc_b <- acc_b + total_b.
+ *   DSL_OPT_COLLIDE_HITS counts the moved (particle, body) pairs of the last pass.
+ *   Integration.  Only in the step drivers (dsl_wcsph_step, dsl_pcisph_step, DSL_PCI_END_STEP), after each step's fold, and
+ *   only while DSL_OPT_BODIES_INTEGRATE is 1; dsl_collide_pass runs the pass and the fold alone.  dt = dsl_params.dt.  Per
+ *   body, (J, tau) = total_b of this pass, R the pose the pass used, a over the three axes:
+ *     1. lin_a <- lin_a + (J_a inv_mass + accel_a dt)
+ *     2. tl = R^T tau;  wl_a = tl_a inv_inertia_a;  ang <- ang + R wl   (the two matrix products row by dot product)
+ *     3. trans_a <- trans_a + dt lin_a   (the new lin)
+ *     4. with w = the new ang: dw = -((w.x q.x + w.y q.y) + w.z q.z),  dx = q.w w.x + (w.y q.z - w.z q.y),
+ *        dy = q.w w.y + (w.z q.x - w.x q.z),  dz = q.w w.z + (w.x q.y - w.y q.x),  hd = 0.5 dt
+ *     5. q' = q + hd (dw, dx, dy, dz) per component;  q <- q' / |q'|;  R from q.
+ *   There is no gyroscopic term (w x I w is left out: the inertia acts as if the body's axes were principal and the spin
+ *   slow against the step).  At the identity, at rest, with zeros everywhere every step is exact: q stays (1, 0, 0, 0),
+ *   R the exact identity, and the pass gives the static pass's bits.
+ * Both launches of a pass (the pass; the fold with the integration as its last act) are timed under DSL_K_COLLIDE. */
+#define DSL_MAX_BODIES 16
+typedef struct dsl_body_props {
+  float inv_mass;
+  float inv_inertia[3];
+  float accel[3];
+  float radius;
+  float restitution;
+} dsl_body_props;
+typedef struct dsl_body_state {
+  float quat[4]; /* w, x, y, z */
+  float trans[3];
+  float lin_vel[3];
+  float ang_vel[3];
+} dsl_body_state;
+int dsl_body_add(dsl_handle *h, const float *dev_volume, const float *host_volume, const float origin[3], const float step[3],
+                 const int32_t dims[3], const dsl_body_props *props, const dsl_body_state *state, int *body_id);
+int dsl_bodies_clear(dsl_handle *h);
+int dsl_body_set_state(dsl_handle *h, int body, const dsl_body_state *state);
+int dsl_body_set_props(dsl_handle *h, int body, const dsl_body_props *props);
+int dsl_body_get_state(dsl_handle *h, int body, dsl_body_state *state, float impulse[3], float torque[3], int reset);
+int dsl_body_query(dsl_handle *h, int body, float *dist /* N */, float *normal /* 3N */);
+
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
 
@@ -894,7 +970,10 @@ enum {
   DSL_OPT_SDF_DISTANCE_MS = 74,    /* (get, blocking) milliseconds of its distance launch, as DSL_OPT_SURFACE_COUNT_MS; */
   DSL_OPT_SDF_SIGN_MS = 75,        /* its sign launches: the marks' memset, the sweep, the parity (0 with DSL_SDF_UNSIGNED) */
   DSL_OPT_COLLIDER_VOLUME = 76,    /* (get) voxels of the volume collider; 0: none */
-  DSL_OPT_COLLIDER_VOLUME_MOVING = 77   /* (get) 1 while a motion is set */
+  DSL_OPT_COLLIDER_VOLUME_MOVING = 77,  /* (get) 1 while a motion is set */
+  DSL_OPT_BODIES = 78,             /* (get) number of rigid bodies (dsl_body_add) */
+  DSL_OPT_BODIES_INTEGRATE = 79    /* (set/get, default 1) 0: the step drivers run the bodies' pass and fold but leave the
+                                      poses alone -- a host that scripts all motion itself */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
