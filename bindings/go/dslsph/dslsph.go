@@ -1147,3 +1147,44 @@ func (e *Engine) BodyQuery(body int) (dist, normal []float32, err error) {
 	err = e.ck(C.dsl_body_query(e.h, C.int(body), (*C.float)(unsafe.Pointer(&dist[0])), (*C.float)(unsafe.Pointer(&normal[0]))))
 	return
 }
+
+// ---- the bodies' contact stage: the wall box and each other (include/dslsph.h: dsl_contact_points) ----
+
+const (
+	// bit 1: walls, bit 2: bodies -- the step drivers detect and solve behind each integration (set/get, default 0);
+	// the entries of the last solve that got past k > 0 (get, blocking)
+	OptBodiesContact  = int(C.DSL_OPT_BODIES_CONTACT)
+	OptBodiesContacts = int(C.DSL_OPT_BODIES_CONTACTS)
+	ContactWalls      = 1
+	ContactBodies     = 2
+)
+
+// ContactPoints: the voxel indices of a body's contact points, ascending (blocking)
+func (e *Engine) ContactPoints(body int) (voxels []int32, err error) {
+	var m C.int64_t
+	if err = e.ck(C.dsl_contact_points(e.h, C.int(body), nil, 0, &m)); err != nil || m == 0 {
+		return
+	}
+	voxels = make([]int32, int(m))
+	err = e.ck(C.dsl_contact_points(e.h, C.int(body), (*C.int32_t)(unsafe.Pointer(&voxels[0])), C.size_t(len(voxels)), &m))
+	return
+}
+
+// ContactPass: detection at the current poses for kinds, whatever the option is, and the solve behind it if asked
+func (e *Engine) ContactPass(kinds int, solve bool) error {
+	s := 0
+	if solve {
+		s = 1
+	}
+	return e.ck(C.dsl_contact_pass(e.h, C.int(kinds), C.int(s)))
+}
+
+// ContactTable: E of the last detection over k bodies, [body][target][9] = S (3), N (3), W, C, D (blocking)
+func (e *Engine) ContactTable(k int) (table []float32, err error) {
+	table = make([]float32, 9*k*(6+k))
+	if len(table) == 0 {
+		return
+	}
+	err = e.ck(C.dsl_contact_table(e.h, (*C.float)(unsafe.Pointer(&table[0])), C.size_t(len(table))))
+	return
+}

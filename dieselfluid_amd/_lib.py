@@ -138,6 +138,9 @@ EXPORTS = {
     "dsl_body_set_props": (C.c_int, [_vp, C.c_int, C.POINTER(BodyProps)]),
     "dsl_body_get_state": (C.c_int, [_vp, C.c_int, C.POINTER(BodyState), _fp, _fp, C.c_int]),
     "dsl_body_query": (C.c_int, [_vp, C.c_int, _fp, _fp]),
+    "dsl_contact_points": (C.c_int, [_vp, C.c_int, _ip, C.c_size_t, C.POINTER(C.c_int64)]),
+    "dsl_contact_pass": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "dsl_contact_table": (C.c_int, [_vp, _fp, C.c_size_t]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

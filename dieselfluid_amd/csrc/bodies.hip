@@ -13,6 +13,7 @@
 //   k_body_query    d and the world-space n against one body, no response
 //   k_bodies_fold   one workgroup per body: the partials in a fixed order, added once into the body's accumulators; then,
 //                   for a step driver, one lane integrates the body's pose and stores it for the next pass
+#include "bodies_device.hpp"
 #include "engine.hpp"
 #include "sph_device.hpp"
 
@@ -22,59 +23,8 @@
 
 namespace dsl {
 
-// A body in device memory: the device writes state and rot (the fold's integration) and acc, the host the rest
-struct BodyRec {
-  const float* vol;
-  Lattice g;
-  dsl_body_props p;
-  dsl_body_state s;  // quat is kept at unit length
-  float rot[9];      // row-major R of quat
-  float acc[6];      // impulse and torque impulse about s.trans since the last reset
-};
-
+// (BodyRec, the pose helpers and body_contact: bodies_device.hpp, shared with contact.hip)
 namespace {
-// q / |q|, |q| = sqrt(((ww + xx) + yy) + zz)
-__host__ __device__ inline void quat_normalize(float (&q)[4]) {
-  const float len = sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  for (int k = 0; k < 4; ++k) q[k] = q[k] / len;
-}
-// the row-major R of q = (w, x, y, z): every product, sum and difference rounded, each parenthesis formed first
-__host__ __device__ inline void quat_to_rot(const float (&q)[4], float (&r)[9]) {
-  const float w = q[0], x = q[1], y = q[2], z = q[3];
-  const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  r[0] = 1.0f - 2.0f * (yy + zz);
-  r[1] = 2.0f * (xy - wz);
-  r[2] = 2.0f * (xz + wy);
-  r[3] = 2.0f * (xy + wz);
-  r[4] = 1.0f - 2.0f * (xx + zz);
-  r[5] = 2.0f * (yz - wx);
-  r[6] = 2.0f * (xz - wy);
-  r[7] = 2.0f * (yz + wx);
-  r[8] = 1.0f - 2.0f * (xx + yy);
-}
-
-// The particle against one body: q = x - trans, xl = R^T q, the cell evaluation at xl, n = R (g / |g|)
-struct BodyContact {
-  float qx, qy, qz, d, nx, ny, nz;
-  bool cell, has_n;
-};
-__device__ __forceinline__ BodyContact body_contact(const BodyRec& m, float px, float py, float pz) {
-  BodyContact k;
-  k.qx = px - m.s.trans[0], k.qy = py - m.s.trans[1], k.qz = pz - m.s.trans[2];
-  const float lx = dot3(m.rot[0], m.rot[3], m.rot[6], k.qx, k.qy, k.qz);
-  const float ly = dot3(m.rot[1], m.rot[4], m.rot[7], k.qx, k.qy, k.qz);
-  const float lz = dot3(m.rot[2], m.rot[5], m.rot[8], k.qx, k.qy, k.qz);
-  const CellEval e = volume_cell_eval(m.g, m.vol, lx, ly, lz);
-  k.cell = e.cell;
-  k.has_n = e.cell && e.mag > 0.f;
-  k.d = e.d;
-  const float lnx = e.gx / e.mag, lny = e.gy / e.mag, lnz = e.gz / e.mag;
-  k.nx = dot3(m.rot[0], m.rot[1], m.rot[2], lnx, lny, lnz);
-  k.ny = dot3(m.rot[3], m.rot[4], m.rot[5], lnx, lny, lnz);
-  k.nz = dot3(m.rot[6], m.rot[7], m.rot[8], lnx, lny, lnz);
-  return k;
-}
-
 // The integration of include/dslsph.h, steps 1 to 5, on one lane: (J, tau) = c, R the pose the pass used.  No gyroscopic term
 __device__ __forceinline__ void body_integrate(BodyRec& m, const float (&c)[6], float dt) {
   float lin[3], ang[3], tl[3], wl[3], q[4], r[9];
@@ -279,6 +229,7 @@ void bodies_release(dsl_handle* h) {
   h->dev_bytes -= h->body_rec.count + h->body_partial.count * sizeof(float);
   release(h->body_rec);
   release(h->body_partial);
+  contact_release(h);
   h->n_bodies = 0;
 }
 }  // namespace
@@ -307,6 +258,8 @@ int bodies_pass(dsl_handle* h, bool integrate) {
   if (rc) return rc;
   h->grid_valid = false;  // positions moved
   h->masks_valid = false;
+  // the bodies against the wall box and each other, at the poses the integration left (contact.hip)
+  if (integrate && h->bodies_contact != 0) return contact_step(h);
   return DSL_OK;
 }
 
@@ -349,6 +302,12 @@ int dsl_body_add(dsl_handle* h, const float* dev_volume, const float* host_volum
   posed(state ? *state : kAtRest, &r);  // (acc: zeros)
   HIP_TRY(h, hipMemcpyAsync(recs(h) + b, &r, sizeof(BodyRec), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the caller's array and `r` are never retained after the call returns)
+  h->body_g[b] = r.g;
+  h->contact_built &= ~(1u << b);
+  // its contact points, before the body exists: a build that fails leaves the bodies as they were (while
+  // DSL_OPT_BODIES_CONTACT is 0 a body gets no list)
+  if (h->bodies_contact != 0)
+    if (int rc = contact_list_of(h, b)) return rc;
   h->n_bodies = b + 1;
   if (body_id) *body_id = b;
   return DSL_OK;

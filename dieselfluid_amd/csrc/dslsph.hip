@@ -1700,6 +1700,7 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
     case DSL_OPT_COLLIDE_CULL: h->col_cull = value != 0.0; return DSL_OK;
     case DSL_OPT_VOLUME_BRICKS: h->vol_bricks = value != 0.0; return DSL_OK;
     case DSL_OPT_BODIES_INTEGRATE: h->bodies_integrate = value != 0.0; return DSL_OK;
+    case DSL_OPT_BODIES_CONTACT: return contact_option_set(h, value);
     case DSL_OPT_COLLIDE_SLAB:
       if (value == 0.0 && h->col_slab && h->c.n_ptr && h->col_tri > 0)
         return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_SLAB cannot go back to 0 while a slab handle holds a "
@@ -1792,6 +1793,8 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_VOLUME_BRICKS: *value = h->vol_bricks ? 1.0 : 0.0; return DSL_OK;
     case DSL_OPT_BODIES: *value = (double)h->n_bodies; return DSL_OK;
     case DSL_OPT_BODIES_INTEGRATE: *value = h->bodies_integrate ? 1.0 : 0.0; return DSL_OK;
+    case DSL_OPT_BODIES_CONTACT:
+    case DSL_OPT_BODIES_CONTACTS: return contact_option_get(h, option, value);  // (the second blocking)
     case DSL_OPT_VOLUME_LDS_BRICKS: return volume_brick_count(h, 0, value);  // (blocking: the kernel counts on the device)
     case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
     case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);

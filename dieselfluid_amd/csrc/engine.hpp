@@ -11,7 +11,8 @@
 //   sdf.hip            implicit colliders: dsl_mesh_distance_volume, dsl_collider_set_volume, the volume collide pass, their kernels
 //   sdf_rigid.hip      the volume collider in rigid motion: dsl_collider_volume_motion, dsl_collider_volume_impulse, their two kernels
 //   bodies.hip         rigid bodies: dsl_body_*, several volume colliders in one pass, the fold that integrates their poses
-// The last six are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
+//   contact.hip        their contact stage: dsl_contact_*, contact points, detection against the wall box and each other, the solve
+// The last seven are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
 // PhaseClock members): the lattice and its one check, the collider's cell evaluation, the arrays that grow on demand and the
 // per-phase event clocks.  The barrier with its LDS drain, the voxel coordinate and the ordered dot product are sph_device.hpp's.
 #pragma once
@@ -240,6 +241,23 @@ struct dsl_handle {
   dsl::DevArray<float> body_vol[DSL_MAX_BODIES];
   dsl::DevArray<float> body_partial;
   float* body_query = nullptr;
+  // their contact stage (contact.hip; DSL_OPT_BODIES_CONTACT): nothing below is allocated while the option is 0 and no
+  // dsl_contact_* call was made.  body_g: the bodies' lattices as dsl_body_add checked them; contact_pts / contact_m: a body's
+  // contact points (voxel indices, ascending) and their number, bit b of contact_built: body b's list exists; contact_scan:
+  // the list build's counts, then offsets, per 256 voxels; contact_meta: one record per body and the block table of the
+  // detection's flattened grid, laid out for contact_k bodies (0: stale); contact_partial: nine words per workgroup and
+  // target; contact_table: E, 9 K (6 + K) words, contact_table_k: the K of the last detection (0: none yet); contact_ctr:
+  // the entries of the last solve that got past k > 0
+  int bodies_contact = 0;
+  dsl::Lattice body_g[DSL_MAX_BODIES] = {};
+  dsl::DevArray<int> contact_pts[DSL_MAX_BODIES];
+  int contact_m[DSL_MAX_BODIES] = {};
+  unsigned contact_built = 0;
+  dsl::DevArray<int> contact_scan;
+  dsl::DevArray<unsigned char> contact_meta;
+  int contact_k = 0, contact_blocks = 0, contact_table_k = 0;
+  dsl::DevArray<float> contact_partial, contact_table;
+  dsl::DevArray<int> contact_ctr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -395,5 +413,13 @@ int collide_volume_rigid_query(dsl_handle* h, float* qd, float* qn);  // dsl_col
 // ---- defined in bodies.hip ----
 void bodies_free(dsl_handle* h);
 int bodies_pass(dsl_handle* h, bool integrate);  // the collide pass while bodies exist: the pass, the fold, the integration
+
+// ---- defined in contact.hip ----
+void contact_release(dsl_handle* h);       // the lists, the tables and the partial sums go, and leave DSL_OPT_DEVICE_BYTES
+int contact_lists(dsl_handle* h);          // the contact points of every body that has none yet (blocking)
+int contact_list_of(dsl_handle* h, int b); // the contact points of the body dsl_body_add is about to publish as b (blocking)
+int contact_step(dsl_handle* h);           // a step driver's detect, table fold and solve for DSL_OPT_BODIES_CONTACT
+int contact_option_set(dsl_handle* h, double value);
+int contact_option_get(dsl_handle* h, int option, double* value);
 
 }  // namespace dsl

@@ -624,6 +624,29 @@ class SPHEngine:
         self._ck(self._L.dsl_body_query(self._h, body, _fp(dist), _fp(nrm)))
         return dist, nrm
 
+    # -- the bodies' contact stage (include/dslsph.h: dsl_contact_points) -----------
+    def contact_points(self, body: int, cap: int | None = None):
+        """(the first min(M, cap) voxel indices of a body's contact points, ascending; M).  cap None: all of them"""
+        m = C.c_int64(0)
+        if cap is None:
+            self._ck(self._L.dsl_contact_points(self._h, body, None, 0, C.byref(m)))
+            cap = int(m.value)
+        out = np.zeros(max(cap, 1), dtype=np.int32)
+        self._ck(self._L.dsl_contact_points(self._h, body, out.ctypes.data_as(C.POINTER(C.c_int32)) if cap > 0 else None, cap,
+                                            C.byref(m)))
+        return out[:min(cap, int(m.value))], int(m.value)
+
+    def contact_pass(self, kinds: int = 3, solve: bool = False):
+        """detection at the current poses (kinds: 1 walls | 2 bodies), and the solve behind it if asked; asynchronous"""
+        self._ck(self._L.dsl_contact_pass(self._h, int(kinds), 1 if solve else 0))
+
+    def contact_table(self) -> np.ndarray:
+        """E of the last detection, (K, 6 + K, 9): S (3), N (3), W, C, D per body and target"""
+        k = int(self.get_option("bodies"))
+        out = np.zeros((k, 6 + k, 9), dtype=np.float32)
+        self._ck(self._L.dsl_contact_table(self._h, _fp(out), out.size))
+        return out
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -780,7 +803,8 @@ class SPHEngine:
                "surface_emit_ms": 60, "surface_vertices": 61, "surface_mesh_vcount_ms": 62, "surface_mesh_vscan_ms": 63,
                "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65,
                "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76,
-               "collider_volume_moving": 77, "bodies": 78, "bodies_integrate": 79}
+               "collider_volume_moving": 77, "bodies": 78, "bodies_integrate": 79, "bodies_contact": 80,
+               "bodies_contacts": 81}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

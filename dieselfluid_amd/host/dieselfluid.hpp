@@ -476,6 +476,29 @@ class SPH {
       if (normal) normal->resize(3 * (size_t)s_.particles_);
       s_.ck(dsl_body_query(s_.h_, id, dist ? dist->data() : nullptr, normal ? normal->data() : nullptr));
     }
+    // The bodies against the wall box and each other (include/dslsph.h: dsl_contact_points).  kinds: 1 walls | 2 bodies;
+    // Contact(kinds) has the step drivers detect and solve behind each integration (DSL_OPT_BODIES_CONTACT), 0 turns it off
+    void Contact(int kinds) { s_.ck(dsl_set_option(s_.h_, DSL_OPT_BODIES_CONTACT, (double)kinds)); }
+    int Contacts() {
+      double v = 0.0;
+      s_.ck(dsl_get_option(s_.h_, DSL_OPT_BODIES_CONTACTS, &v));
+      return (int)v;
+    }
+    std::vector<int32_t> ContactPoints(int id) {
+      int64_t m = 0;
+      s_.ck(dsl_contact_points(s_.h_, id, nullptr, 0, &m));
+      std::vector<int32_t> out((size_t)m);
+      if (m > 0) s_.ck(dsl_contact_points(s_.h_, id, out.data(), out.size(), &m));
+      return out;
+    }
+    void ContactPass(int kinds, bool solve) { s_.ck(dsl_contact_pass(s_.h_, kinds, solve ? 1 : 0)); }
+    // E of the last detection: [body][target][9] = S (3), N (3), W, C, D
+    std::vector<float> ContactTable() {
+      const size_t K = (size_t)Count();
+      std::vector<float> out(9 * K * (6 + K));
+      s_.ck(dsl_contact_table(s_.h_, out.data(), out.size()));
+      return out;
+    }
 
    private:
     SPH& s_;

@@ -651,6 +651,64 @@ int dsl_body_set_props(dsl_handle *h, int body, const dsl_body_props *props);
 int dsl_body_get_state(dsl_handle *h, int body, dsl_body_state *state, float impulse[3], float torque[3], int reset);
 int dsl_body_query(dsl_handle *h, int body, float *dist /* N */, float *normal /* 3N */);
 
+/* Contact of the rigid bodies with the wall box and with each other (csrc/contact.hip; tests/contact_ref.py restates the rule
+ * operation for operation).  Opt-in: DSL_OPT_BODIES_CONTACT (default 0) is bit 1 (walls) | bit 2 (bodies).  While it is 0 and
+ * none of the three calls below is made, nothing changes: no launch, no allocation, no bit.  The rule is build-defined, with
+ * the arithmetic conventions of the bodies' rule above (float32, one rounding per operation, nothing fused, the ordered dot
+ * product, (u x v).x = u.y v.z - u.z v.y and cyclic with each product and difference rounded, `/` and sqrt correctly
+ * rounded), the same in both math modes.
+ *   Contact points.  A voxel of a body's volume is a contact point when its value is finite and <= 0 and at least one of
+ *   its up to six axis neighbours inside the lattice is finite and > 0: the innermost shell.  A body's list is the set of
+ *   such voxels as int32 linear indices (x fastest), ascending, built on the device from the library's copy of the volume by
+ *   a count, a prefix sum and an emit.  A point's body-frame coordinate is origin + step * (float)index per axis, the rule
+ *   of dsl_field_volume.  An unsigned (thin-shell) volume has no point: such a body never initiates a contact (and, d < 0
+ *   never holding in it, no other body's point finds it: only the fluid does).  The lists are built for all bodies when the
+ *   option first becomes non-zero or one of the calls below first needs them, and at dsl_body_add while the option is
+ *   non-zero -- never at dsl_body_add while it is 0.  dsl_body_add builds the list before the body exists: if that fails
+ *   (DSL_ERR_NOMEM) there is no new body.  They, the partial sums and the table are counted in DSL_OPT_DEVICE_BYTES and freed
+ *   by dsl_bodies_clear and dsl_destroy.
+ *   Detection.  For every body A at its current pose (R, trans) and every point pl of A: q_a = (R[a][0] pl.x + R[a][1] pl.y)
+ *   + R[a][2] pl.z, x_a = trans_a + q_a.  Each body has 6 + K targets.  Wall target t = 2 a + side, only with bit 1 and
+ *   dsl_params.walls != 0: side 0: pen = box_min[a] - x_a, n = +e_a; side 1: pen = x_a - box_max[a], n = -e_a; the point
+ *   contributes when pen > 0.  Body target t = 6 + B, B != A, only with bit 2: the bodies' pass's evaluation of x against B
+ *   (r = x - trans_B, xl = R_B^T r, the cell, d, g, n = R_B (g / |g|)); the point contributes when there is a cell, |g| > 0
+ *   and d < 0, with pen = -d.  No bounding test skips a body.  A contribution is the eight sums (pen q.x, pen q.y, pen q.z,
+ *   pen n.x, pen n.y, pen n.z, pen, 1) and the depth pen; a point that does not contribute gives nine +0.  Per (A, t):
+ *   workgroup b owns points [256 b, 256 b + 256) of A's list and reduces the sums with the tree of
+ *   dsl_collider_volume_motion; the total adds the partials lane-strided and ascending from +0, then the same tree over the
+ *   256 lane sums; the depth D is the maximum.  No float atomics.  The table is E[A][t] = (S[3], N[3], W, C, D): nine
+ *   floats per entry, K (6 + K) entries, nine +0 for t = 6 + A and for a kind that is off.
+ *   Solve.  One lane, A ascending and inside A t ascending, every quantity of a body read from its record as the earlier
+ *   contacts of this solve left it.  An entry is skipped unless W > 0.  qc_a = S_a / W.  Wall: n is the axis vector.  Body:
+ *   len = sqrt(dot3(N, N)), skipped unless len > 0, n_a = N_a / len.  Iw_X(t) is the integration's step 2: tl = R^T t,
+ *   wl_a = tl_a inv_inertia_a, R wl.  tA = Iw_A(qc x n), kA = inv_mass_A + dot3(tA x qc, n).  Body target:
+ *   rB_a = (trans_A_a + qc_a) - trans_B_a, tB = Iw_B(rB x n), kB = inv_mass_B + dot3(tB x rB, n), k = kA + kB; wall: k = kA.
+ *   Skipped unless k > 0: a kinematic body is moved by nothing, but others bounce off it.  uA = lin_A + ang_A x qc,
+ *   uB = lin_B + ang_B x rB (0 for a wall), vn = dot3(uA - uB, n).  When vn < 0: e = A's restitution against a wall, fminf
+ *   of the two against a body; f = (1 + e) vn; j = (-f) / k; lin_A_a += (j inv_mass_A) n_a; ang_A_a += j tA_a;
+ *   lin_B_a -= (j inv_mass_B) n_a; ang_B_a -= j tB_a.  Push-out against a wall, when inv_mass_A > 0: trans_A_a += D n_a.
+ *   Against a body, with s = inv_mass_A + inv_mass_B, when s > 0: trans_A_a += ((0.5 D)(inv_mass_A / s)) n_a,
+ *   trans_B_a -= ((0.5 D)(inv_mass_B / s)) n_a -- the half because the pair is met twice, as (A, B) and as (B, A).  The
+ *   quaternion and R are not touched.
+ *   Limits.  There is no friction and no stacking solver; a body rests with its innermost voxel shell on the wall; a body
+ *   that moves more than its own thickness per step tunnels; contact between bodies reaches as deep as B's band, because
+ *   beyond it |g| = 0.
+ *   Where it runs.  Only in the step drivers (dsl_wcsph_step, dsl_pcisph_step, DSL_PCI_END_STEP), after each step's fold and
+ *   integration, only while DSL_OPT_BODIES_INTEGRATE is 1 and DSL_OPT_BODIES_CONTACT is non-zero: pass, fold + integrate,
+ *   detect, table fold, solve; the contact launches are timed under DSL_K_COLLIDE.  dsl_collide_pass stays as it is.
+ * dsl_contact_points: the first min(M, cap) voxel indices of a body's list and M (*count, may be NULL); cap = 0 with a NULL
+ *   array is the counting call.  Blocking.
+ * dsl_contact_pass: detection at the current poses for `kinds` (bit 1 | bit 2), whatever the option is; solve != 0 adds the
+ *   solve.  Asynchronous -- but the first call after bodies were added (and, likewise, the first step of a step driver with
+ *   the option on) blocks: it builds the lists that are missing and lays out the detection's grid, with two stream
+ *   synchronisations.  DSL_ERR_INVALID: no bodies, or unknown kinds.
+ * dsl_contact_table: the last detection's 9 K (6 + K) floats; count must match.  Blocking.
+ * All three: DSL_ERR_UNSUPPORTED on a slab handle; an unknown body id is refused as in dsl_body_query; a refused call changes
+ * nothing. */
+int dsl_contact_points(dsl_handle *h, int body, int32_t *host_voxels, size_t cap, int64_t *count);
+int dsl_contact_pass(dsl_handle *h, int kinds, int solve);
+int dsl_contact_table(dsl_handle *h, float *host, size_t count);
+
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
 
@@ -972,8 +1030,12 @@ enum {
   DSL_OPT_COLLIDER_VOLUME = 76,    /* (get) voxels of the volume collider; 0: none */
   DSL_OPT_COLLIDER_VOLUME_MOVING = 77,  /* (get) 1 while a motion is set */
   DSL_OPT_BODIES = 78,             /* (get) number of rigid bodies (dsl_body_add) */
-  DSL_OPT_BODIES_INTEGRATE = 79    /* (set/get, default 1) 0: the step drivers run the bodies' pass and fold but leave the
+  DSL_OPT_BODIES_INTEGRATE = 79,   /* (set/get, default 1) 0: the step drivers run the bodies' pass and fold but leave the
                                       poses alone -- a host that scripts all motion itself */
+  DSL_OPT_BODIES_CONTACT = 80,     /* (set/get, default 0) bit 1: the bodies against the wall box, bit 2: against each other,
+                                      behind each step's integration (dsl_contact_pass); other values: DSL_ERR_INVALID.  A
+                                      list build that fails with DSL_ERR_NOMEM leaves the option as it was */
+  DSL_OPT_BODIES_CONTACTS = 81     /* (get, blocking) entries of the last solve that got past k > 0 */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);

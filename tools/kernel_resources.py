@@ -4,7 +4,8 @@ per kernel from -Rpass-analysis=kernel-resource-usage; optionally keep the assem
 
   python tools/kernel_resources.py [--source collide.hip] [--filter SUBSTR] [--asm /tmp/dsl.s] [-D MACRO ...]
 
---source: a file of dieselfluid_amd/csrc; dslsph.hip (the engine, the default) or collide.hip (the collider's kernels).
+--source: a file of dieselfluid_amd/csrc; dslsph.hip (the engine, the default), collide.hip (the collider's kernels), or any
+other unit with kernels of its own, such as bodies.hip or contact.hip (the rigid bodies and their contact stage).
 """
 import argparse
 import os
