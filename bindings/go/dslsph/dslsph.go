@@ -1188,3 +1188,110 @@ func (e *Engine) ContactTable(k int) (table []float32, err error) {
 	err = e.ck(C.dsl_contact_table(e.h, (*C.float)(unsafe.Pointer(&table[0])), C.size_t(len(table))))
 	return
 }
+
+// ---- sources and sinks: fluid emitted and removed on the device (include/dslsph.h: dsl_particles_append) ----
+
+const (
+	MaxEmitters = int(C.DSL_MAX_EMITTERS)
+	MaxSinks    = int(C.DSL_MAX_SINKS)
+	// the timing id of the emit launch, the sink count and the compaction's launches (dsl_timing_get)
+	KSources = int(C.DSL_K_SOURCES)
+	// emitters and sinks in place; particles emitted, layers skipped for want of room, particles removed (all get);
+	// the step drivers apply the sinks at steps s with s % every == 0 (set/get, default 8; 0: only RemoveParticles does)
+	OptEmitters    = int(C.DSL_OPT_EMITTERS)
+	OptSinks       = int(C.DSL_OPT_SINKS)
+	OptEmitted     = int(C.DSL_OPT_EMITTED)
+	OptEmitSkipped = int(C.DSL_OPT_EMIT_SKIPPED)
+	OptRemoved     = int(C.DSL_OPT_REMOVED)
+	OptSinkEvery   = int(C.DSL_OPT_SINK_EVERY)
+)
+
+// Emitter: lattice point (a, b) of the face lies at Origin + a U + b V; a layer every Period-th step from FirstStep on
+type Emitter struct {
+	Origin, U, V, Velocity [3]float32
+	Nu, Nv                 int
+	Ellipse                bool
+	Period                 int
+	FirstStep, MaxLayers   int64
+}
+
+// Sink: particles inside [Min, Max) go (Outside: the ones outside it); entries may be +-Inf
+type Sink struct {
+	Min, Max [3]float32
+	Outside  bool
+}
+
+// syncCount: the library's n_particles has changed: refresh the copy that SetParams sends back and that sizes the buffers
+func (e *Engine) syncCount() error {
+	return e.ck(C.dsl_get_params(e.h, &e.Params))
+}
+
+// SyncCount: after solver steps with an emitter or a sink in place; returns the particle count
+func (e *Engine) SyncCount() (int, error) {
+	err := e.syncCount()
+	return int(e.Params.n_particles), err
+}
+
+// AppendParticles: new fluid particles behind the current ones, xyz interleaved; velocities nil: zeros (blocking)
+func (e *Engine) AppendParticles(positions, velocities []float32) error {
+	if len(positions) == 0 {
+		return nil
+	}
+	var v *C.float
+	if len(velocities) > 0 {
+		v = (*C.float)(unsafe.Pointer(&velocities[0]))
+	}
+	if err := e.ck(C.dsl_particles_append(e.h, (*C.float)(unsafe.Pointer(&positions[0])), v, C.size_t(len(positions)/3))); err != nil {
+		return err
+	}
+	return e.syncCount()
+}
+
+func (e *Engine) AddEmitter(em Emitter) (id int, err error) {
+	var d C.dsl_emitter
+	for a := 0; a < 3; a++ {
+		d.origin[a], d.u[a], d.v[a], d.velocity[a] = C.float(em.Origin[a]), C.float(em.U[a]), C.float(em.V[a]), C.float(em.Velocity[a])
+	}
+	d.nu, d.nv, d.period = C.int32_t(em.Nu), C.int32_t(em.Nv), C.int32_t(em.Period)
+	if em.Ellipse {
+		d.shape = 1
+	}
+	d.first_step, d.max_layers = C.int64_t(em.FirstStep), C.int64_t(em.MaxLayers)
+	var k C.int
+	err = e.ck(C.dsl_emitter_add(e.h, &d, &k))
+	return int(k), err
+}
+
+func (e *Engine) ClearEmitters() error { return e.ck(C.dsl_emitters_clear(e.h)) }
+
+// Emit: one layer of the emitter now, between steps
+func (e *Engine) Emit(emitter int) error {
+	if err := e.ck(C.dsl_emit(e.h, C.int(emitter))); err != nil {
+		return err
+	}
+	return e.syncCount()
+}
+
+func (e *Engine) AddSink(s Sink) (id int, err error) {
+	var d C.dsl_sink
+	for a := 0; a < 3; a++ {
+		d.box_min[a], d.box_max[a] = C.float(s.Min[a]), C.float(s.Max[a])
+	}
+	if s.Outside {
+		d.outside = 1
+	}
+	var k C.int
+	err = e.ck(C.dsl_sink_add(e.h, &d, &k))
+	return int(k), err
+}
+
+func (e *Engine) ClearSinks() error { return e.ck(C.dsl_sinks_clear(e.h)) }
+
+// RemoveParticles: applies the sinks now; returns how many particles went (blocking)
+func (e *Engine) RemoveParticles() (removed int64, err error) {
+	var r C.int64_t
+	if err = e.ck(C.dsl_particles_remove(e.h, &r)); err != nil {
+		return
+	}
+	return int64(r), e.syncCount()
+}

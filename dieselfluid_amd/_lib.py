@@ -76,6 +76,18 @@ class BodyState(C.Structure):
     _fields_ = [("quat", C.c_float * 4), ("trans", C.c_float * 3), ("lin_vel", C.c_float * 3), ("ang_vel", C.c_float * 3)]
 
 
+class Emitter(C.Structure):
+    """dsl_emitter (include/dslsph.h)."""
+    _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("nu", C.c_int32), ("nv", C.c_int32),
+                ("shape", C.c_int32), ("velocity", C.c_float * 3), ("period", C.c_int32), ("first_step", C.c_int64),
+                ("max_layers", C.c_int64)]
+
+
+class Sink(C.Structure):
+    """dsl_sink (include/dslsph.h)."""
+    _fields_ = [("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("outside", C.c_int32)]
+
+
 # dsl_transport (include/dslsph.h): the host's own transport behind dsl_comm_create_custom
 TR_GROUP = C.CFUNCTYPE(C.c_int, C.c_void_p)
 TR_XFER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -141,6 +153,13 @@ EXPORTS = {
     "dsl_contact_points": (C.c_int, [_vp, C.c_int, _ip, C.c_size_t, C.POINTER(C.c_int64)]),
     "dsl_contact_pass": (C.c_int, [_vp, C.c_int, C.c_int]),
     "dsl_contact_table": (C.c_int, [_vp, _fp, C.c_size_t]),
+    "dsl_particles_append": (C.c_int, [_vp, _fp, _fp, C.c_size_t]),
+    "dsl_emitter_add": (C.c_int, [_vp, C.POINTER(Emitter), C.POINTER(C.c_int)]),
+    "dsl_emitters_clear": (C.c_int, [_vp]),
+    "dsl_emit": (C.c_int, [_vp, C.c_int]),
+    "dsl_sink_add": (C.c_int, [_vp, C.POINTER(Sink), C.POINTER(C.c_int)]),
+    "dsl_sinks_clear": (C.c_int, [_vp]),
+    "dsl_particles_remove": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

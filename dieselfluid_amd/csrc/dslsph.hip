@@ -215,7 +215,7 @@ namespace {
 
 int drain_timing(dsl_handle* h) {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (int k = 0; k < DSL_K_COUNT; ++k) {
+  for (int k = 0; k < DSL_K_END; ++k) {
     for (auto& pr : h->pending[k]) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
@@ -778,6 +778,7 @@ void free_all(dsl_handle* h) {
   (void)hipFree(h->vol_ctr);
   surface_free(h);
   sdf_free(h);
+  sources_free(h);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1152,6 +1153,9 @@ int dsl_add_boundary_particles(dsl_handle* h, const float* host_positions, size_
     return fail(h, DSL_ERR_INVALID, "dsl_add_boundary_particles: count must be a positive multiple of 3");
   if (h->c.n_ptr) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_add_boundary_particles: not available in slab mode");
   if (h->ids_global) return fail(h, DSL_ERR_INVALID, "dsl_add_boundary_particles: particle ids were replaced (dsl_set_ids)");
+  if (h->n_emitters > 0 || h->n_sinks > 0 || h->count_changed)
+    return fail(h, DSL_ERR_UNSUPPORTED, "dsl_add_boundary_particles: not available while emitters or sinks exist (dsl_emitters_clear, "
+                                        "dsl_sinks_clear), nor once an append or a removal has changed the particle count");
   const int nb = (int)(count / 3);
   if ((long long)h->n + nb > h->cap)
     return fail(h, DSL_ERR_NOMEM, "dsl_add_boundary_particles: dsl_params.capacity leaves no room (needs n_particles + all boundary particles)");
@@ -1461,6 +1465,7 @@ constexpr int kSkinRetry = 2048;
 bool skin_usable(const dsl_handle* h) {
   return h->skin > 0.0f && h->steps >= h->skin_retry_at && h->prm.math_mode == DSL_MATH_FAST && !h->lsh && h->c.slab_axis < 0 && !h->c.n_ptr && h->nb == 0 &&
          h->col_tri == 0 && !h->colv_on && h->n_bodies == 0 &&  // (the collide pass moves particles behind the kernel that measures displacement)
+         h->n_emitters == 0 && h->n_sinks == 0 &&  // (the lists are built for a particle count; sources and sinks change it)
          !h->pci_active && h->c.xsph_eps == 0.0f && h->c.st_kappa == 0.0f && use_tiled(h) && h->nmask != nullptr &&
          (h->c.wcsph_pressure_force != 0 || h->c.wcsph_viscosity != 0);
 }
@@ -1637,6 +1642,7 @@ int dsl_wcsph_step(dsl_handle* h, int nsteps) {
     }
     if (h->skin_live)
       if (int rc = skin_settle(h)) return rc;
+    if (int rc = sources_step(h)) return rc;        // (only while an emitter or a sink exists: this step's sinks, then its layers)
     if (int rc = build_grid(h, false)) return rc;  // NN(): geometric neighbour rule -> every step
     if (int rc = density_pass(h)) return rc;        // DensityAll   wcsph.go:18
     if (int rc = force_integrate(h)) return rc;     // ExternalAll, PressureAll, Update wcsph.go:19-21
@@ -1701,6 +1707,7 @@ int dsl_set_option(dsl_handle* h, int option, double value) {
     case DSL_OPT_VOLUME_BRICKS: h->vol_bricks = value != 0.0; return DSL_OK;
     case DSL_OPT_BODIES_INTEGRATE: h->bodies_integrate = value != 0.0; return DSL_OK;
     case DSL_OPT_BODIES_CONTACT: return contact_option_set(h, value);
+    case DSL_OPT_SINK_EVERY: return sources_option_set(h, value);
     case DSL_OPT_COLLIDE_SLAB:
       if (value == 0.0 && h->col_slab && h->c.n_ptr && h->col_tri > 0)
         return fail(h, DSL_ERR_INVALID, "dsl_set_option: DSL_OPT_COLLIDE_SLAB cannot go back to 0 while a slab handle holds a "
@@ -1795,6 +1802,12 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_BODIES_INTEGRATE: *value = h->bodies_integrate ? 1.0 : 0.0; return DSL_OK;
     case DSL_OPT_BODIES_CONTACT:
     case DSL_OPT_BODIES_CONTACTS: return contact_option_get(h, option, value);  // (the second blocking)
+    case DSL_OPT_EMITTERS:
+    case DSL_OPT_SINKS:
+    case DSL_OPT_EMITTED:
+    case DSL_OPT_EMIT_SKIPPED:
+    case DSL_OPT_REMOVED:
+    case DSL_OPT_SINK_EVERY: return sources_option_get(h, option, value);
     case DSL_OPT_VOLUME_LDS_BRICKS: return volume_brick_count(h, 0, value);  // (blocking: the kernel counts on the device)
     case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
     case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);
@@ -1890,6 +1903,7 @@ namespace dsl {
 int pci_begin_step(dsl_handle* h) {
   const DevConsts& c = h->c;
   h->pci_rows_live = false;  // (the sort re-numbers the particles: the query rows start afresh)
+  if (int rc = sources_step(h)) return rc;  // (only while an emitter or a sink exists: this step's sinks, then its layers)
   if (int rc = pci_drift_check(h)) return rc;
   if (int rc = build_grid(h, false)) return rc;
   if (int rc = density_pass(h)) return rc;        // DensityAll  pcisph_darwin.go:44
@@ -2121,6 +2135,8 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (axis >= 0 && h->col_tri > 0 && !h->col_slab) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a collider mesh is not supported in slab mode");
   if (axis >= 0 && h->colv_on) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a volume collider is not supported in slab mode");
   if (axis >= 0 && h->n_bodies > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: rigid bodies are not supported in slab mode");
+  if (axis >= 0 && (h->n_emitters > 0 || h->n_sinks > 0))
+    return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: emitters and sinks are not supported in slab mode (dsl_emitters_clear, dsl_sinks_clear)");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;
@@ -2424,7 +2440,7 @@ int dsl_timing_enable(dsl_handle* h, int on) {
 int dsl_timing_reset(dsl_handle* h) {
   CHECK_HANDLE_ONLY(h);
   if (int rc = drain_timing(h)) return rc;
-  for (int k = 0; k < DSL_K_COUNT; ++k) {
+  for (int k = 0; k < DSL_K_END; ++k) {
     h->total_ms[k] = 0.0;
     h->launches[k] = 0;
   }
@@ -2432,7 +2448,7 @@ int dsl_timing_reset(dsl_handle* h) {
 }
 int dsl_timing_get(dsl_handle* h, int kid, double* avg_ms, int64_t* launches) {
   CHECK_HANDLE_ONLY(h);
-  if (kid < 0 || kid >= DSL_K_COUNT) return fail(h, DSL_ERR_INVALID, "bad kernel id");
+  if (kid < 0 || kid >= DSL_K_END) return fail(h, DSL_ERR_INVALID, "bad kernel id");
   if (int rc = drain_timing(h)) return rc;
   if (avg_ms) *avg_ms = h->launches[kid] ? h->total_ms[kid] / (double)h->launches[kid] : 0.0;
   if (launches) *launches = h->launches[kid];

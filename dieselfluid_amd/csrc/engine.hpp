@@ -12,7 +12,8 @@
 //   sdf_rigid.hip      the volume collider in rigid motion: dsl_collider_volume_motion, dsl_collider_volume_impulse, their two kernels
 //   bodies.hip         rigid bodies: dsl_body_*, several volume colliders in one pass, the fold that integrates their poses
 //   contact.hip        their contact stage: dsl_contact_*, contact points, detection against the wall box and each other, the solve
-// The last seven are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
+//   sources.hip        sources and sinks: dsl_particles_append, dsl_emit*, dsl_sink*, dsl_particles_remove, their seven kernels
+// The seven before the last are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
 // PhaseClock members): the lattice and its one check, the collider's cell evaluation, the arrays that grow on demand and the
 // per-phase event clocks.  The barrier with its LDS drain, the voxel coordinate and the ordered dot product are sph_device.hpp's.
 #pragma once
@@ -258,14 +259,29 @@ struct dsl_handle {
   int contact_k = 0, contact_blocks = 0, contact_table_k = 0;
   dsl::DevArray<float> contact_partial, contact_table;
   dsl::DevArray<int> contact_ctr;
+  // sources and sinks (sources.hip; dsl_emitter_add, dsl_sink_add): nothing below is allocated, and no step launches
+  // anything for it, while there is no emitter, no sink and none of the calls was made.  emit_pts / emit_m: an emitter's
+  // kept lattice points, b * nu + a each, in layer order, and their number; emit_layers: the layers it has emitted;
+  // src_ctr: the sink count's word; src_scan: the compaction's counts, then offsets, per 256 host indices and the total
+  // behind them.  count_changed: an append, an emission or a removal has changed the particle count of this handle
+  int n_emitters = 0, n_sinks = 0;
+  dsl_emitter emitters[DSL_MAX_EMITTERS] = {};
+  dsl::DevArray<int> emit_pts[DSL_MAX_EMITTERS];
+  int emit_m[DSL_MAX_EMITTERS] = {};
+  int64_t emit_layers[DSL_MAX_EMITTERS] = {};
+  dsl_sink sinks[DSL_MAX_SINKS] = {};
+  int sink_every = 8;  // DSL_OPT_SINK_EVERY
+  int64_t src_emitted = 0, src_skipped = 0, src_removed = 0;
+  bool count_changed = false;
+  dsl::DevArray<int> src_ctr, src_scan;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
   int timing = 0;  // 0 off, 1 every kernel, 2 the step's dominant kernels only
   std::vector<hipEvent_t> pool;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[DSL_K_COUNT];
-  double total_ms[DSL_K_COUNT] = {};
-  int64_t launches[DSL_K_COUNT] = {};
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[DSL_K_END];
+  double total_ms[DSL_K_END] = {};
+  int64_t launches[DSL_K_END] = {};
 };
 
 namespace dsl {
@@ -421,5 +437,12 @@ int contact_list_of(dsl_handle* h, int b); // the contact points of the body dsl
 int contact_step(dsl_handle* h);           // a step driver's detect, table fold and solve for DSL_OPT_BODIES_CONTACT
 int contact_option_set(dsl_handle* h, double value);
 int contact_option_get(dsl_handle* h, int option, double* value);
+
+// ---- defined in sources.hip ----
+void sources_free(dsl_handle* h);
+// a step driver's sinks and emitters of the step about to run, in front of its neighbour build; nothing while none exists
+int sources_step(dsl_handle* h);
+int sources_option_set(dsl_handle* h, double value);                // DSL_OPT_SINK_EVERY
+int sources_option_get(dsl_handle* h, int option, double* value);  // DSL_OPT_EMITTERS .. DSL_OPT_SINK_EVERY
 
 }  // namespace dsl

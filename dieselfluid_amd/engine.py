@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import BodyProps, BodyState, DslError, Params, Stats, load_library
+from ._lib import BodyProps, BodyState, DslError, Emitter, Params, Sink, Stats, load_library
 
 BUF = {
     "positions": 0, "velocities": 1, "forces": 2, "densities": 3, "pressures": 4,
@@ -22,6 +22,7 @@ KERNEL_IDS = {
     "cell_rank": 0, "scan": 1, "scatter": 2, "density": 3, "force_integrate": 4, "pressure": 5, "viscous": 6,
     "gradient": 7, "external": 8, "update": 9, "pci_predict": 10, "pci_density": 11, "tile_list": 12,
     "neigh_lists": 13, "collide": 14, "volume": 15, "surface": 16, "surface_mesh": 17, "sdf": 18,
+    "sources": 19,
 }
 SDF_UNSIGNED = 1  # DSL_SDF_UNSIGNED
 
@@ -218,7 +219,7 @@ class SPHEngine:
 
     @property
     def n(self) -> int:
-        """live particle count (changes only in slab mode)"""
+        """live particle count: changes in slab mode, and with append_particles, emitters and sinks"""
         n = C.c_int(0)
         self._ck(self._L.dsl_get_count(self._h, C.byref(n), None))
         return n.value
@@ -647,6 +648,48 @@ class SPHEngine:
         self._ck(self._L.dsl_contact_table(self._h, _fp(out), out.size))
         return out
 
+    # -- sources and sinks (include/dslsph.h: dsl_particles_append .. dsl_particles_remove) ---
+    def append_particles(self, positions, velocities=None):
+        """new fluid particles behind the current ones (host indices n .. n + len - 1); velocities None: zeros"""
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        v = None if velocities is None else np.ascontiguousarray(velocities, dtype=np.float32).reshape(-1)
+        if v is not None and v.size != p.size:
+            raise ValueError("positions and velocities must have the same shape")
+        self._ck(self._L.dsl_particles_append(self._h, _fp(p) if p.size else None, None if v is None else _fp(v), p.size // 3))
+
+    def add_emitter(self, origin, u, v, nu: int, nv: int, velocity, period: int = 1, first_step: int = 0, max_layers: int = 0,
+                    shape: int = 0) -> int:
+        """a face of nu x nv lattice points origin + a u + b v (shape 1: the inscribed ellipse) that emits a layer every
+        period-th step from first_step on, max_layers of them (0: no limit); returns the emitter's id"""
+        e = Emitter((C.c_float * 3)(*origin), (C.c_float * 3)(*u), (C.c_float * 3)(*v), int(nu), int(nv), int(shape),
+                    (C.c_float * 3)(*velocity), int(period), int(first_step), int(max_layers))
+        k = C.c_int(-1)
+        self._ck(self._L.dsl_emitter_add(self._h, C.byref(e), C.byref(k)))
+        return k.value
+
+    def clear_emitters(self):
+        self._ck(self._L.dsl_emitters_clear(self._h))
+
+    def emit(self, emitter: int):
+        """one layer of the emitter now, between steps"""
+        self._ck(self._L.dsl_emit(self._h, int(emitter)))
+
+    def add_sink(self, box_min, box_max, outside: bool = False) -> int:
+        """particles inside the box [box_min, box_max) go (outside: the ones outside it); entries may be +-inf"""
+        s = Sink((C.c_float * 3)(*box_min), (C.c_float * 3)(*box_max), 1 if outside else 0)
+        k = C.c_int(-1)
+        self._ck(self._L.dsl_sink_add(self._h, C.byref(s), C.byref(k)))
+        return k.value
+
+    def clear_sinks(self):
+        self._ck(self._L.dsl_sinks_clear(self._h))
+
+    def remove_particles(self) -> int:
+        """applies the sinks now; returns how many particles went"""
+        r = C.c_int64(0)
+        self._ck(self._L.dsl_particles_remove(self._h, C.byref(r)))
+        return int(r.value)
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -804,7 +847,8 @@ class SPHEngine:
                "surface_mesh_vemit_ms": 64, "surface_mesh_iemit_ms": 65,
                "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76,
                "collider_volume_moving": 77, "bodies": 78, "bodies_integrate": 79, "bodies_contact": 80,
-               "bodies_contacts": 81}
+               "bodies_contacts": 81,
+               "emitters": 88, "sinks": 89, "emitted": 90, "emit_skipped": 91, "removed": 92, "sink_every": 93}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

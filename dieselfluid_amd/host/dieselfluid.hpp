@@ -505,6 +505,65 @@ class SPH {
   };
   Bodies RigidBodies() { return Bodies(*this); }
 
+  // Sources and sinks (include/dslsph.h: dsl_particles_append): fluid emitted from lattice faces and removed by boxes, on the
+  // device, at step counts fixed in advance.  The reference has no counterpart.  N() follows every call made here; after
+  // solver steps with an emitter or a sink in place, SyncCount() brings it up to date.
+  struct Emitter {
+    float Origin[3] = {0.f, 0.f, 0.f}, U[3] = {1.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 1.f};  // point (a, b): Origin + a U + b V
+    int Nu = 1, Nv = 1;
+    bool Ellipse = false;  // the ellipse inscribed in the Nu x Nv rectangle
+    float Velocity[3] = {0.f, 0.f, 0.f};
+    int Period = 1;  // a layer every Period-th step from FirstStep on (the handle's step counter), MaxLayers of them (0: no limit)
+    int64_t FirstStep = 0, MaxLayers = 0;
+  };
+  struct Sink {
+    float Min[3] = {0.f, 0.f, 0.f}, Max[3] = {0.f, 0.f, 0.f};  // [Min, Max) per axis; entries may be +-infinity
+    bool Outside = false;                                      // true: particles outside the box go
+  };
+  int SyncCount() {
+    ck(dsl_get_params(h_, &prm_));
+    particles_ = prm_.n_particles;
+    return particles_;
+  }
+  // xyz interleaved, as Positions() returns them; velocities empty: zeros
+  void AppendParticles(const std::vector<float>& positions, const std::vector<float>& velocities = {}) {
+    ck(dsl_particles_append(h_, positions.data(), velocities.empty() ? nullptr : velocities.data(), positions.size() / 3));
+    SyncCount();
+  }
+  int AddEmitter(const Emitter& e) {
+    dsl_emitter d{};
+    for (int a = 0; a < 3; ++a) d.origin[a] = e.Origin[a], d.u[a] = e.U[a], d.v[a] = e.V[a], d.velocity[a] = e.Velocity[a];
+    d.nu = e.Nu, d.nv = e.Nv, d.shape = e.Ellipse ? 1 : 0, d.period = e.Period;
+    d.first_step = e.FirstStep, d.max_layers = e.MaxLayers;
+    int id = -1;
+    ck(dsl_emitter_add(h_, &d, &id));
+    return id;
+  }
+  void ClearEmitters() { ck(dsl_emitters_clear(h_)); }
+  // one layer now, between steps
+  void Emit(int emitter) {
+    ck(dsl_emit(h_, emitter));
+    SyncCount();
+  }
+  int AddSink(const Sink& s) {
+    dsl_sink d{};
+    for (int a = 0; a < 3; ++a) d.box_min[a] = s.Min[a], d.box_max[a] = s.Max[a];
+    d.outside = s.Outside ? 1 : 0;
+    int id = -1;
+    ck(dsl_sink_add(h_, &d, &id));
+    return id;
+  }
+  void ClearSinks() { ck(dsl_sinks_clear(h_)); }
+  // applies the sinks now; returns how many particles went
+  int64_t RemoveParticles() {
+    int64_t gone = 0;
+    ck(dsl_particles_remove(h_, &gone));
+    SyncCount();
+    return gone;
+  }
+  // the step drivers apply the sinks at steps s with s % every == 0 (DSL_OPT_SINK_EVERY; 0: only RemoveParticles does)
+  void SinkEvery(int every) { ck(dsl_set_option(h_, DSL_OPT_SINK_EVERY, (double)every)); }
+
   // The fluid's surface as a mesh.Mesh (README.MD:38 "SPH/Fluid Surfaces"; the reference's renderer draws meshes): the
   // iso-surface of SPHField.Interpolate on the lattice origin + step * (i, j, k), evaluated, triangulated and wound on the
   // device (include/dslsph.h: dsl_field_surface).  density = false: the pressure field.  The buffer is sized from a guess --

@@ -155,7 +155,9 @@ enum {
   DSL_K_SURFACE = 16,     /* dsl_surface_extract: its count, scan and emit launches, one entry each */
   DSL_K_SURFACE_MESH = 17, /* dsl_surface_extract_indexed: its vertex count, vertex scan, vertex emit and index emit */
   DSL_K_SDF = 18,          /* dsl_mesh_distance_volume: prep, brick count, scan, brick fill, distance, sweep, sign, one entry each */
-  DSL_K_COUNT = 19
+  DSL_K_COUNT = 19,        /* the ids above: the step's and the scene's kernels */
+  DSL_K_SOURCES = 19,      /* sources and sinks: the emit launch, the sink count, the compaction's launches, one entry each */
+  DSL_K_END = 20           /* one past the last id: dsl_timing_get takes 0 .. DSL_K_END - 1 */
 };
 
 typedef struct dsl_handle dsl_handle;
@@ -709,6 +711,85 @@ int dsl_contact_points(dsl_handle *h, int body, int32_t *host_voxels, size_t cap
 int dsl_contact_pass(dsl_handle *h, int kinds, int solve);
 int dsl_contact_table(dsl_handle *h, float *host, size_t count);
 
+/* Sources and sinks: fluid particles created and removed on the device, so the particle count of a handle changes between
+ * steps.  The rule is build-defined (the reference has no sources; tests/sources_ref.py restates it operation for operation)
+ * and the same in both math modes.
+ *
+ * A new particle -- appended by the host or emitted -- takes the next host index N (the indices run on: N .. N + n_new - 1) and
+ *   has the given position and velocity, force = force_reset, pressure 0, density 0 and P/rho^2 0 (what a fresh handle's
+ *   zero-filled arrays read) until the next density pass, and, while PCISPH is active, predictor state equal to its position
+ *   and velocity (what dsl_pcisph_begin would copy).  Forces that are not uniform are kept: force_reset goes into the new
+ *   slots of the array.  The neighbour table is stale afterwards; densities stay on their particles.  dsl_get_params returns
+ *   the new n_particles and dsl_set_params accepts exactly it.
+ * A layer of an emitter: lattice point (a, b) of the face, 0 <= a < nu, 0 <= b < nv, lies at
+ *   (origin_c + (float)a * u_c) + (float)b * v_c per component c, every product and sum rounded once to float32, never fused
+ *   (dsl_field_volume's discipline: a caller reproduces every bit).  shape 0 keeps every point; shape 1, the ellipse inscribed
+ *   in the rectangle, keeps (a, b) when (2a - (nu-1))^2 nv^2 + (2b - (nv-1))^2 nu^2 <= (nu nv)^2 in 64-bit integers (the
+ *   centre is always kept).  The kept points, b ascending and inside it a ascending, are the layer: M particles with host
+ *   indices N .. N + M - 1 in that order, every one with the emitter's velocity.
+ * The schedule: at the start of step s (s = dsl_stats.steps before the step) the step drivers dsl_wcsph_step,
+ *   dsl_pcisph_step and DSL_PCI_BEGIN_STEP first apply the sinks when DSL_OPT_SINK_EVERY is not 0 and s % every == 0, then
+ *   visit the emitters in ascending id: emitter e emits one layer when s >= first_step, (s - first_step) % period == 0 and
+ *   it has emitted fewer than max_layers layers (max_layers 0: no limit).  A layer that does not fit dsl_params.capacity is
+ *   skipped whole -- never a partial layer, never an error from the step; DSL_OPT_EMIT_SKIPPED counts it and it does not
+ *   count towards max_layers.  All of it happens at step counts fixed in advance: results do not depend on how the steps were
+ *   grouped into calls.  Emission needs no synchronisation (the host knows every count); a look of the sinks is one count
+ *   kernel and one 4-byte read-back, and the compaction runs only when the count is not 0.
+ * A sink is a box: inside = (x_a >= box_min_a && x_a < box_max_a) on all three axes (entries may be +-infinity, a NaN
+ *   coordinate is never inside); a particle goes when, for some sink, inside != (outside != 0).  Survivors keep their
+ *   relative host order -- the new host index of a survivor is the number of survivors with a smaller old index -- and every
+ *   per-particle buffer follows its particle: positions, velocities, forces, densities, pressures, the PCISPH predictor
+ *   state.  Densities keep their standing (held, and fresh if they were); the neighbour table is stale.  The slot order
+ *   afterwards is the library's choice (dsl_download_ids describes it).  A handle is never emptied: when every particle
+ *   would go, the one with the smallest host index stays.
+ *
+ * dsl_particles_append: n_new particles from host arrays of 3 n_new floats (host_velocities NULL: zeros).  Blocking.
+ *   DSL_ERR_NOMEM (dsl_last_error names capacity) when N + n_new > capacity; DSL_ERR_INVALID on a NULL array, n_new = 0 or
+ *   a non-finite entry.
+ * dsl_emitter_add: up to DSL_MAX_EMITTERS; *id (may be NULL) is the emitter's index.  Blocking: it builds the list of kept
+ *   points on the host and uploads it, one int32 word per point (counted in DSL_OPT_DEVICE_BYTES).  DSL_ERR_INVALID
+ *   (dsl_last_error names the field): a ninth emitter, nu, nv or period < 1, nu * nv > 2^20, u or v all zero, a non-finite
+ *   entry, first_step or max_layers < 0, an unknown shape.  dsl_emitters_clear removes all of them and frees the lists.
+ * dsl_emit: one layer of emitter `emitter` now, between steps, for a host that drives the passes itself; it counts towards
+ *   max_layers (DSL_ERR_INVALID once they are used up, or for an unknown id) and a layer that does not fit is refused with
+ *   DSL_ERR_NOMEM.  Asynchronous.
+ * dsl_sink_add: up to DSL_MAX_SINKS.  DSL_ERR_INVALID: a ninth sink, a NaN entry, box_min > box_max.  dsl_sinks_clear
+ *   removes all of them.
+ * dsl_particles_remove: applies the sinks now; *removed (may be NULL) is the number of particles that went.  Blocking.
+ *
+ * DSL_ERR_UNSUPPORTED from all of them but the two clear calls, with dsl_last_error naming what to remove first: a slab
+ * handle (and dsl_slab_config refuses while emitters or sinks exist), DSL_NEIGH_LSH_REF, a handle with boundary particles
+ * (fluid stays in front; dsl_add_boundary_particles refuses while emitters or sinks exist and once the count has changed),
+ * after dsl_set_ids.  While the caller's stream is being captured a step that would emit or look returns
+ * DSL_ERR_UNSUPPORTED: a replayed graph cannot change its grids or wait for a read-back.  A refused call changes nothing.
+ * The skin step is not taken while an emitter or a sink exists.  Colliders, bodies, contact, field operators, volumes and
+ * surfaces work on the count of the moment.  Limits: no jitter and no test for fluid in front of a face (a host that wants
+ * either appends itself); dt is constant, so the spacing of the layers, period * dt * |velocity|, is the host's arithmetic;
+ * no sources on slab ranks.  Every launch is timed under DSL_K_SOURCES.  With no emitter, no sink and none of these calls
+ * made: no launch, no allocation, no bit changes. */
+#define DSL_MAX_EMITTERS 8
+#define DSL_MAX_SINKS 8
+typedef struct dsl_emitter {
+  float origin[3], u[3], v[3]; /* lattice point (a, b) of the face: origin + a u + b v, world */
+  int32_t nu, nv;              /* 1 <= nu, nv; nu * nv <= 2^20 */
+  int32_t shape;               /* 0 rectangle, 1 ellipse inscribed in it */
+  float velocity[3];           /* every emitted particle starts with it */
+  int32_t period;              /* >= 1: a layer every period-th step */
+  int64_t first_step;          /* absolute, on the handle's step counter (dsl_stats.steps) */
+  int64_t max_layers;          /* 0: no limit */
+} dsl_emitter;
+typedef struct dsl_sink {
+  float box_min[3], box_max[3];
+  int32_t outside; /* 0: particles inside the box go; otherwise: particles outside it */
+} dsl_sink;
+int dsl_particles_append(dsl_handle *h, const float *host_positions, const float *host_velocities, size_t n_new);
+int dsl_emitter_add(dsl_handle *h, const dsl_emitter *emitter, int *id);
+int dsl_emitters_clear(dsl_handle *h);
+int dsl_emit(dsl_handle *h, int emitter);
+int dsl_sink_add(dsl_handle *h, const dsl_sink *sink, int *id);
+int dsl_sinks_clear(dsl_handle *h);
+int dsl_particles_remove(dsl_handle *h, int64_t *removed);
+
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
 
@@ -1035,7 +1116,15 @@ enum {
   DSL_OPT_BODIES_CONTACT = 80,     /* (set/get, default 0) bit 1: the bodies against the wall box, bit 2: against each other,
                                       behind each step's integration (dsl_contact_pass); other values: DSL_ERR_INVALID.  A
                                       list build that fails with DSL_ERR_NOMEM leaves the option as it was */
-  DSL_OPT_BODIES_CONTACTS = 81     /* (get, blocking) entries of the last solve that got past k > 0 */
+  DSL_OPT_BODIES_CONTACTS = 81,    /* (get, blocking) entries of the last solve that got past k > 0 */
+  /* sources and sinks */
+  DSL_OPT_EMITTERS = 88,           /* (get) number of emitters (dsl_emitter_add) */
+  DSL_OPT_SINKS = 89,              /* (get) number of sinks (dsl_sink_add) */
+  DSL_OPT_EMITTED = 90,            /* (get) particles emitted so far, by the step drivers and by dsl_emit */
+  DSL_OPT_EMIT_SKIPPED = 91,       /* (get) layers the step drivers skipped because they did not fit the capacity */
+  DSL_OPT_REMOVED = 92,            /* (get) particles the sinks removed so far */
+  DSL_OPT_SINK_EVERY = 93          /* (set/get, default 8) the step drivers apply the sinks at steps s with s % every == 0;
+                                      0: only dsl_particles_remove does.  Negative or above 2^30: DSL_ERR_INVALID */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
