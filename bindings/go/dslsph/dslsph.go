@@ -28,6 +28,7 @@ import "C"
 import (
 	"errors"
 	"fmt"
+	"io"
 	"unsafe"
 )
 
@@ -1294,4 +1295,120 @@ func (e *Engine) RemoveParticles() (removed int64, err error) {
 		return
 	}
 	return int64(r), e.syncCount()
+}
+
+// The frame recorder (include/dslsph.h: dsl_recorder_set): animation frames packed on the device during a run and copied
+// to pinned host memory behind the steps that follow -- "Fluid Animation Export" (README.MD:39), in place of the blocking
+// read-back of every position after every step (pcisph_gpu_darwin.go:276-279).
+const (
+	RecVelocity = int(C.DSL_REC_VELOCITY)
+	RecDensity  = int(C.DSL_REC_DENSITY)
+	RecF32      = int(C.DSL_REC_F32)
+	RecQ16      = int(C.DSL_REC_Q16)
+	// frames recorded, dropped for want of a released slot, landed and unreleased (all get); milliseconds of the last
+	// frame's bounds + pack launches and of its copy (get, blocking; 0 unless TimingEnable(1) held)
+	OptRecordFrames  = int(C.DSL_OPT_RECORD_FRAMES)
+	OptRecordDropped = int(C.DSL_OPT_RECORD_DROPPED)
+	OptRecordReady   = int(C.DSL_OPT_RECORD_READY)
+	OptRecordPackMs  = int(C.DSL_OPT_RECORD_PACK_MS)
+	OptRecordCopyMs  = int(C.DSL_OPT_RECORD_COPY_MS)
+)
+
+// Recorder: a frame at steps s >= FirstStep with (s - FirstStep) % Every == 0, MaxFrames of them (0: no limit); every
+// Stride-th particle in host order; Fields = RecVelocity | RecDensity beside the positions; Encoding RecF32 or RecQ16, the
+// latter against [BoxMin, BoxMax] or, with AutoBox, each frame's own bounds; Slots frames (1..64) of pinned host memory
+type Recorder struct {
+	Every, Stride, Fields, Encoding, Slots int
+	AutoBox                                bool
+	BoxMin, BoxMax                         [3]float32
+	FirstStep, MaxFrames                   int64
+}
+
+func (r *Recorder) spec() C.dsl_recorder {
+	var d C.dsl_recorder
+	d.every, d.stride, d.fields = C.int32_t(r.Every), C.int32_t(r.Stride), C.int32_t(r.Fields)
+	d.encoding, d.slots = C.int32_t(r.Encoding), C.int32_t(r.Slots)
+	if r.AutoBox {
+		d.auto_box = 1
+	}
+	for a := 0; a < 3; a++ {
+		d.box_min[a], d.box_max[a] = C.float(r.BoxMin[a]), C.float(r.BoxMax[a])
+	}
+	d.first_step, d.max_frames = C.int64_t(r.FirstStep), C.int64_t(r.MaxFrames)
+	return d
+}
+
+// FrameBytes: the size of a frame of n particles under the spec; 0 for a spec SetRecorder would refuse
+func (r *Recorder) FrameBytes(n int) int {
+	d := r.spec()
+	return int(C.dsl_record_frame_bytes(&d, C.int(n)))
+}
+
+// SetRecorder: stores the spec and allocates (blocking); nil: the recorder is off and everything is freed
+func (e *Engine) SetRecorder(r *Recorder) error {
+	if r == nil {
+		return e.ck(C.dsl_recorder_set(e.h, nil))
+	}
+	d := r.spec()
+	return e.ck(C.dsl_recorder_set(e.h, &d))
+}
+
+// RecordNow: one frame of the current state, between steps
+func (e *Engine) RecordNow() error { return e.ck(C.dsl_record_now(e.h)) }
+
+// PollFrames: frames recorded so far, landed and unreleased, dropped; never blocks
+func (e *Engine) PollFrames() (recorded, ready, dropped int64, err error) {
+	var a, b, c C.int64_t
+	err = e.ck(C.dsl_record_poll(e.h, &a, &b, &c))
+	return int64(a), int64(b), int64(c), err
+}
+
+// NextFrame: the oldest unreleased frame, copied out of its pinned slot and released (waits for its copy only)
+func (e *Engine) NextFrame() ([]byte, error) {
+	var p unsafe.Pointer
+	var n C.size_t
+	if err := e.ck(C.dsl_record_peek(e.h, &p, &n)); err != nil {
+		return nil, err
+	}
+	out := C.GoBytes(p, C.int(n))
+	return out, e.ck(C.dsl_record_release(e.h))
+}
+
+// ReadFrameInto: the oldest unreleased frame copied into buf (at least FrameBytes long) and released, without an allocation
+func (e *Engine) ReadFrameInto(buf []byte) error {
+	if len(buf) == 0 {
+		return errors.New("ReadFrameInto: empty buffer")
+	}
+	return e.ck(C.dsl_record_read(e.h, unsafe.Pointer(&buf[0]), C.size_t(len(buf))))
+}
+
+// AnimationFileHeader: the 16 bytes an animation file starts with: "DSLANIM\0", version 1, zero; the frames follow as
+// the library wrote them, each finding the next through its frame_bytes
+func AnimationFileHeader() []byte {
+	return []byte{'D', 'S', 'L', 'A', 'N', 'I', 'M', 0, 1, 0, 0, 0, 0, 0, 0, 0}
+}
+
+// WriteTo: every frame that has been recorded and not released, oldest first, written to w as it is and released; the
+// bytes written.  A file is AnimationFileHeader() and then any number of these calls
+func (e *Engine) WriteTo(w io.Writer) (int64, error) {
+	var total int64
+	for {
+		recorded, _, _, err := e.PollFrames()
+		if err != nil {
+			return total, err
+		}
+		var p unsafe.Pointer
+		var n C.size_t
+		if recorded == 0 || C.dsl_record_peek(e.h, &p, &n) != C.DSL_OK {
+			return total, nil // (nothing unreleased is left)
+		}
+		k, err := w.Write(C.GoBytes(p, C.int(n)))
+		total += int64(k)
+		if err != nil {
+			return total, err
+		}
+		if err := e.ck(C.dsl_record_release(e.h)); err != nil {
+			return total, err
+		}
+	}
 }

@@ -88,6 +88,22 @@ class Sink(C.Structure):
     _fields_ = [("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("outside", C.c_int32)]
 
 
+class Recorder(C.Structure):
+    """dsl_recorder (include/dslsph.h)."""
+    _fields_ = [("every", C.c_int32), ("stride", C.c_int32), ("fields", C.c_int32), ("encoding", C.c_int32), ("slots", C.c_int32),
+                ("auto_box", C.c_int32), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("first_step", C.c_int64),
+                ("max_frames", C.c_int64)]
+
+
+class FrameHeader(C.Structure):
+    """the 128-byte header a recorded frame starts with (include/dslsph.h: the frame recorder)."""
+    _fields_ = [("magic", C.c_uint32), ("header_bytes", C.c_uint32), ("frame_bytes", C.c_uint64), ("step", C.c_int64),
+                ("n_particles", C.c_int32), ("count", C.c_int32), ("stride", C.c_int32), ("fields", C.c_int32),
+                ("encoding", C.c_int32), ("auto_box", C.c_int32), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("bounds_min", C.c_float * 3), ("bounds_max", C.c_float * 3), ("dt", C.c_float), ("finite", C.c_int32),
+                ("zero", C.c_uint8 * 24)]
+
+
 # dsl_transport (include/dslsph.h): the host's own transport behind dsl_comm_create_custom
 TR_GROUP = C.CFUNCTYPE(C.c_int, C.c_void_p)
 TR_XFER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -160,6 +176,13 @@ EXPORTS = {
     "dsl_sink_add": (C.c_int, [_vp, C.POINTER(Sink), C.POINTER(C.c_int)]),
     "dsl_sinks_clear": (C.c_int, [_vp]),
     "dsl_particles_remove": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "dsl_recorder_set": (C.c_int, [_vp, C.POINTER(Recorder)]),
+    "dsl_record_frame_bytes": (C.c_size_t, [C.POINTER(Recorder), C.c_int]),
+    "dsl_record_now": (C.c_int, [_vp]),
+    "dsl_record_poll": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dsl_record_peek": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "dsl_record_release": (C.c_int, [_vp]),
+    "dsl_record_read": (C.c_int, [_vp, _vp, C.c_size_t]),
     "dsl_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "dsl_sync": (C.c_int, [_vp]),
     "dsl_set_stream": (C.c_int, [_vp, _vp]),

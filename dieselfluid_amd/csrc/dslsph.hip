@@ -779,6 +779,7 @@ void free_all(dsl_handle* h) {
   surface_free(h);
   sdf_free(h);
   sources_free(h);
+  record_free(h);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   for (auto& v : h->pending)
     for (auto& pr : v) {
@@ -1632,6 +1633,7 @@ int skin_settle(dsl_handle* h) {
 int dsl_wcsph_step(dsl_handle* h, int nsteps) {
   CHECK_HANDLE_ONLY(h);
   for (int s = 0; s < nsteps; ++s) {
+    if (int rc = record_step(h)) return rc;  // (only while a recorder is set: the frame of the state before this step)
     // (forces that differ from force_reset -- uploaded ones, before the first Update -- take one plain step first)
     if (skin_usable(h) && (h->skin_live || h->forces_uniform)) {
       if (!h->skin_live)
@@ -1808,6 +1810,11 @@ int dsl_get_option(dsl_handle* h, int option, double* value) {
     case DSL_OPT_EMIT_SKIPPED:
     case DSL_OPT_REMOVED:
     case DSL_OPT_SINK_EVERY: return sources_option_get(h, option, value);
+    case DSL_OPT_RECORD_FRAMES:
+    case DSL_OPT_RECORD_DROPPED:
+    case DSL_OPT_RECORD_READY:
+    case DSL_OPT_RECORD_PACK_MS:
+    case DSL_OPT_RECORD_COPY_MS: return record_option_get(h, option, value);  // (the two times blocking)
     case DSL_OPT_VOLUME_LDS_BRICKS: return volume_brick_count(h, 0, value);  // (blocking: the kernel counts on the device)
     case DSL_OPT_VOLUME_FALLBACK_BRICKS: return volume_brick_count(h, 1, value);
     case DSL_OPT_VOLUME_EMPTY_BRICKS: return volume_brick_count(h, 2, value);
@@ -1903,6 +1910,7 @@ namespace dsl {
 int pci_begin_step(dsl_handle* h) {
   const DevConsts& c = h->c;
   h->pci_rows_live = false;  // (the sort re-numbers the particles: the query rows start afresh)
+  if (int rc = record_step(h)) return rc;   // (only while a recorder is set: the frame of the state before this step)
   if (int rc = sources_step(h)) return rc;  // (only while an emitter or a sink exists: this step's sinks, then its layers)
   if (int rc = pci_drift_check(h)) return rc;
   if (int rc = build_grid(h, false)) return rc;
@@ -2137,6 +2145,8 @@ int dsl_slab_config(dsl_handle* h, int axis, float lo, float hi) {
   if (axis >= 0 && h->n_bodies > 0) return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: rigid bodies are not supported in slab mode");
   if (axis >= 0 && (h->n_emitters > 0 || h->n_sinks > 0))
     return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: emitters and sinks are not supported in slab mode (dsl_emitters_clear, dsl_sinks_clear)");
+  if (axis >= 0 && h->rec)
+    return fail(h, DSL_ERR_UNSUPPORTED, "dsl_slab_config: a frame recorder is not supported in slab mode (dsl_recorder_set(NULL))");
   int ncur = 0;
   if (int rc = host_count(h, &ncur)) return rc;
   h->c.slab_axis = axis;
@@ -2429,7 +2439,7 @@ int dsl_get_stats(dsl_handle* h, dsl_stats* out) {
 int dsl_sync(dsl_handle* h) {
   CHECK_HANDLE_ONLY(h);
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DSL_OK;
+  return record_sync(h);  // (only while a recorder is set: the frames on their way to their slots have landed too)
 }
 
 int dsl_timing_enable(dsl_handle* h, int on) {

@@ -13,7 +13,8 @@
 //   bodies.hip         rigid bodies: dsl_body_*, several volume colliders in one pass, the fold that integrates their poses
 //   contact.hip        their contact stage: dsl_contact_*, contact points, detection against the wall box and each other, the solve
 //   sources.hip        sources and sinks: dsl_particles_append, dsl_emit*, dsl_sink*, dsl_particles_remove, their seven kernels
-// The seven before the last are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
+//   record.hip         the frame recorder: dsl_recorder_set, dsl_record_*, the step drivers' hook, their four kernels
+// The seven before the last two are the lattice units; what they share is lattice.hpp (included here, since the handle holds its DevArray and
 // PhaseClock members): the lattice and its one check, the collider's cell evaluation, the arrays that grow on demand and the
 // per-phase event clocks.  The barrier with its LDS drain, the voxel coordinate and the ordered dot product are sph_device.hpp's.
 #pragma once
@@ -35,6 +36,7 @@ namespace dsl {
 // the lists are built where the particles will be about half way through the lists' life: the fastest particle may use up
 // this fraction of the displacement budget at the build itself (DSL_OPT_SKIN_PREDICT; 0: built where the particles are)
 constexpr float kSkinPredict = 0.8f;
+struct Recorder;  // record.hip
 }  // namespace dsl
 
 struct dsl_handle {
@@ -274,6 +276,8 @@ struct dsl_handle {
   int64_t src_emitted = 0, src_skipped = 0, src_removed = 0;
   bool count_changed = false;
   dsl::DevArray<int> src_ctr, src_scan;
+  // the frame recorder (record.hip; dsl_recorder_set): nullptr: none -- no launch, no allocation, no step looks further
+  dsl::Recorder* rec = nullptr;
   std::string err;
   SlabLink* link = nullptr;  // dsl_slab_attach: the slab's RCCL link to its neighbours (slab_link.hip)
   // timing
@@ -444,5 +448,13 @@ void sources_free(dsl_handle* h);
 int sources_step(dsl_handle* h);
 int sources_option_set(dsl_handle* h, double value);                // DSL_OPT_SINK_EVERY
 int sources_option_get(dsl_handle* h, int option, double* value);  // DSL_OPT_EMITTERS .. DSL_OPT_SINK_EVERY
+
+// ---- defined in record.hip ----
+void record_free(dsl_handle* h);
+int record_frame_due(dsl_handle* h);  // the frame of the step about to run, if the schedule asks for one
+// a step driver's hook, ahead of everything of the step (its sinks and emitters included); nothing while no recorder is set
+inline int record_step(dsl_handle* h) { return h->rec ? record_frame_due(h) : DSL_OK; }
+int record_option_get(dsl_handle* h, int option, double* value);  // DSL_OPT_RECORD_FRAMES .. DSL_OPT_RECORD_COPY_MS
+int record_sync(dsl_handle* h);  // dsl_sync's share: waits for the copy stream; nothing while no recorder is set
 
 }  // namespace dsl

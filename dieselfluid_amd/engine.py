@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import BodyProps, BodyState, DslError, Emitter, Params, Sink, Stats, load_library
+from ._lib import BodyProps, BodyState, DslError, Emitter, Params, Recorder, Sink, Stats, load_library
 
 BUF = {
     "positions": 0, "velocities": 1, "forces": 2, "densities": 3, "pressures": 4,
@@ -690,6 +690,59 @@ class SPHEngine:
         self._ck(self._L.dsl_particles_remove(self._h, C.byref(r)))
         return int(r.value)
 
+    # -- the frame recorder (include/dslsph.h: dsl_recorder_set .. dsl_record_read; animation.py decodes and files the frames) ---
+    REC_FIELDS = {"velocities": 1, "densities": 2}
+    REC_ENCODINGS = {"f32": 0, "q16": 1}
+
+    @staticmethod
+    def recorder_spec(every: int = 1, stride: int = 1, fields=(), encoding="f32", slots: int = 4, box=None, first_step: int = 0,
+                      max_frames: int = 0) -> Recorder:
+        """a dsl_recorder: fields an iterable of "velocities" / "densities" (or the bit mask), encoding "f32" / "q16" (or the
+        number), box None: each Q16 frame's own bounds (auto_box), else (box_min, box_max)"""
+        bits = fields if isinstance(fields, int) else sum(SPHEngine.REC_FIELDS[f] for f in fields)
+        enc = encoding if isinstance(encoding, int) else SPHEngine.REC_ENCODINGS[encoding]
+        lo, hi = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)) if box is None else box
+        return Recorder(int(every), int(stride), int(bits), int(enc), int(slots), 1 if (box is None and enc == 1) else 0, (C.c_float * 3)(*lo),
+                        (C.c_float * 3)(*hi), int(first_step), int(max_frames))
+
+    def set_recorder(self, spec=None, **kw):
+        """a frame every `every`-th step from first_step on (recorder_spec's arguments, or a Recorder); set_recorder(None)
+        with no arguments turns it off and frees everything"""
+        if spec is None and not kw:
+            self._ck(self._L.dsl_recorder_set(self._h, None))
+            return None
+        spec = spec if spec is not None else self.recorder_spec(**kw)
+        self._ck(self._L.dsl_recorder_set(self._h, C.byref(spec)))
+        return spec
+
+    def record_frame_bytes(self, spec: Recorder, n: int) -> int:
+        return int(self._L.dsl_record_frame_bytes(C.byref(spec), int(n)))
+
+    def record_now(self):
+        """one frame of the current state, between steps"""
+        self._ck(self._L.dsl_record_now(self._h))
+
+    def record_poll(self):
+        """(recorded, ready, dropped); never blocks"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.dsl_record_poll(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def peek_frame(self) -> np.ndarray:
+        """the oldest unreleased frame as a uint8 view of its pinned slot: valid until release_frame"""
+        ptr, size = C.c_void_p(), C.c_size_t(0)
+        self._ck(self._L.dsl_record_peek(self._h, C.byref(ptr), C.byref(size)))
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(size.value,))
+
+    def release_frame(self):
+        self._ck(self._L.dsl_record_release(self._h))
+
+    def read_frame(self) -> bytes:
+        """the oldest unreleased frame, copied out and released (animation.decode_frame reads it)"""
+        out = bytes(self.peek_frame())
+        self.release_frame()
+        return out
+
     # -- SPHField operators no solver calls (sph_field.go:124-135,203-294) ---------
     def field_div(self, tensor: str = "velocities") -> np.ndarray:
         out = np.empty(self.n_fluid, dtype=np.float32)
@@ -848,7 +901,8 @@ class SPHEngine:
                "sdf_active_bricks": 72, "sdf_visits": 73, "sdf_distance_ms": 74, "sdf_sign_ms": 75, "collider_volume": 76,
                "collider_volume_moving": 77, "bodies": 78, "bodies_integrate": 79, "bodies_contact": 80,
                "bodies_contacts": 81,
-               "emitters": 88, "sinks": 89, "emitted": 90, "emit_skipped": 91, "removed": 92, "sink_every": 93}
+               "emitters": 88, "sinks": 89, "emitted": 90, "emit_skipped": 91, "removed": 92, "sink_every": 93,
+               "record_frames": 96, "record_dropped": 97, "record_ready": 98, "record_pack_ms": 99, "record_copy_ms": 100}
 
     def set_option(self, name: str, value: float):
         self._ck(self._L.dsl_set_option(self._h, self.OPTIONS[name], float(value)))

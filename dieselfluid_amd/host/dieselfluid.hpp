@@ -23,6 +23,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -563,6 +564,66 @@ class SPH {
   }
   // the step drivers apply the sinks at steps s with s % every == 0 (DSL_OPT_SINK_EVERY; 0: only RemoveParticles does)
   void SinkEvery(int every) { ck(dsl_set_option(h_, DSL_OPT_SINK_EVERY, (double)every)); }
+
+  // The frame recorder (include/dslsph.h: dsl_recorder_set) -- "Fluid Animation Export" (README.MD:39): frames packed on the
+  // device at step counts fixed in advance and copied to pinned host memory behind the steps that follow, in place of the
+  // reference's blocking read-back of every position after every step (pcisph_gpu_darwin.go:276-279).
+  struct Recorder {
+    int Every = 1, Stride = 1;  // a frame at steps s >= FirstStep with (s - FirstStep) % Every == 0; every Stride-th particle
+    bool Velocities = false, Densities = false;  // beside the positions
+    bool Q16 = false;            // 16-bit planes: positions against [BoxMin, BoxMax] or, with AutoBox, each frame's own bounds
+    bool AutoBox = true;
+    float BoxMin[3] = {0.f, 0.f, 0.f}, BoxMax[3] = {0.f, 0.f, 0.f};
+    int Slots = 4;               // 1..64 frames of pinned host memory
+    int64_t FirstStep = 0, MaxFrames = 0;  // MaxFrames 0: no limit
+  };
+  void SetRecorder(const Recorder& r) {
+    dsl_recorder d{};
+    d.every = r.Every, d.stride = r.Stride, d.slots = r.Slots;
+    d.fields = (r.Velocities ? DSL_REC_VELOCITY : 0) | (r.Densities ? DSL_REC_DENSITY : 0);
+    d.encoding = r.Q16 ? DSL_REC_Q16 : DSL_REC_F32;
+    d.auto_box = (r.Q16 && r.AutoBox) ? 1 : 0;
+    for (int a = 0; a < 3; ++a) d.box_min[a] = r.BoxMin[a], d.box_max[a] = r.BoxMax[a];
+    d.first_step = r.FirstStep, d.max_frames = r.MaxFrames;
+    ck(dsl_recorder_set(h_, &d));
+  }
+  void ClearRecorder() { ck(dsl_recorder_set(h_, nullptr)); }
+  void RecordNow() { ck(dsl_record_now(h_)); }  // one frame of the current state, between steps
+  // frames recorded so far; *ready: landed and unreleased; *dropped: found no released slot.  Never blocks
+  int64_t PollFrames(int64_t* ready = nullptr, int64_t* dropped = nullptr) {
+    int64_t recorded = 0;
+    ck(dsl_record_poll(h_, &recorded, ready, dropped));
+    return recorded;
+  }
+  // the oldest unreleased frame, copied out and released (waits for its copy only)
+  std::vector<unsigned char> NextFrame() {
+    const void* frame = nullptr;
+    size_t bytes = 0;
+    ck(dsl_record_peek(h_, &frame, &bytes));
+    std::vector<unsigned char> out((const unsigned char*)frame, (const unsigned char*)frame + bytes);
+    ck(dsl_record_release(h_));
+    return out;
+  }
+  // The animation file: 16 bytes -- "DSLANIM\0", u32 version 1, u32 zero -- then the frames back to back as the library
+  // wrote them (each finds the next through its frame_bytes).  Writes the header and every unreleased frame, oldest first;
+  // append = true: the frames only, behind a file that has its header.  Returns the frames written
+  int WriteAnimation(const std::string& path, bool append = false) {
+    std::FILE* f = std::fopen(path.c_str(), append ? "ab" : "wb");
+    if (!f) throw std::runtime_error("WriteAnimation: cannot open " + path);
+    const unsigned char head[16] = {'D', 'S', 'L', 'A', 'N', 'I', 'M', 0, 1, 0, 0, 0, 0, 0, 0, 0};
+    bool ok = append || std::fwrite(head, 1, sizeof(head), f) == sizeof(head);
+    int frames = 0;
+    const void* frame = nullptr;
+    size_t bytes = 0;
+    while (ok && dsl_record_peek(h_, &frame, &bytes) == DSL_OK) {  // (DSL_ERR_INVALID: nothing unreleased is left)
+      ok = std::fwrite(frame, 1, bytes, f) == bytes;
+      ck(dsl_record_release(h_));
+      frames += 1;
+    }
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok) throw std::runtime_error("WriteAnimation: write to " + path + " failed");
+    return frames;
+  }
 
   // The fluid's surface as a mesh.Mesh (README.MD:38 "SPH/Fluid Surfaces"; the reference's renderer draws meshes): the
   // iso-surface of SPHField.Interpolate on the lattice origin + step * (i, j, k), evaluated, triangulated and wound on the

@@ -790,6 +790,89 @@ int dsl_sink_add(dsl_handle *h, const dsl_sink *sink, int *id);
 int dsl_sinks_clear(dsl_handle *h);
 int dsl_particles_remove(dsl_handle *h, int64_t *removed);
 
+/* The frame recorder: animation frames packed on the device during a run ("Fluid Animation Export", README.MD:39; the
+ * reference reads every position back after every step and blocks, pcisph_gpu_darwin.go:276-279).  A recorder makes the step
+ * drivers capture a frame every `every`-th step: two small launches reduce the captured particles' bounds, one packs the
+ * frame -- host order, every stride-th particle, float32 or 16-bit -- into a staging frame in device memory, and one
+ * hipMemcpyAsync on a copy stream of the library's own moves it to a slot of pinned host memory behind the steps that follow.
+ * The step stream never waits for the host; it waits on the device only when both staging frames still have their copies
+ * outstanding.  The skin step stays on: the pack reads the slot -> particle map where it lives, on the device.  The rule is
+ * build-defined (tests/record_ref.py restates it operation for operation) and the same in both math modes.
+ *
+ * A frame is self-describing, little-endian: a 128-byte header, then the planes, each starting at the next multiple of 128
+ * bytes; frame_bytes is the end of the last plane rounded up to a multiple of 128, and the padding is zero.  The header:
+ *     0 u32 magic 0x464C5344 ("DSLF")     4 u32 128 (the header's size)     8 u64 frame_bytes     16 i64 step
+ *    24 i32 n_particles (N at that step)  28 i32 count M = ceil(N / stride) 32 i32 stride         36 i32 fields
+ *    40 i32 encoding    44 i32 auto_box (1 or 0; 0 for F32)   48 f32[3] box_min   60 f32[3] box_max (the box Q16 was encoded against; zeros for F32)
+ *    72 f32[3] bounds_min   84 f32[3] bounds_max   96 f32 dt   100 i32 finite   104 .. 127 zero
+ * The planes: positions, then velocities if DSL_REC_VELOCITY, then densities if DSL_REC_DENSITY; xyz interleaved, entry m
+ *   belongs to host index m * stride; fluid particles only.  DSL_REC_F32: 12 M, 12 M and 4 M bytes of float32, bit for bit what
+ *   dsl_download / dsl_download_decimated would return at that moment (densities: those the last density pass left, zeros on
+ *   a fresh handle).  DSL_REC_Q16: 6 M bytes of uint16 x 3, 6 M of float16 x 3, 2 M of float16.
+ * The bounds run over the captured particles whose three coordinates are finite; `finite` is their number.  Minimum and
+ *   maximum are those of the total order of the key bits ^ (bits >> 31 ? 0xffffffff : 0x80000000) on the float's bits, so -0
+ *   lies below +0; with no finite particle they are +inf / -inf.  (Minimum, maximum and an integer count do not depend on the
+ *   order of a reduction: any order gives the same bits.)
+ * DSL_REC_Q16, per axis, against the box [lo, hi] -- the spec's box_min / box_max, or with auto_box the frame's own bounds:
+ *   scale = 65535.0f / (hi - lo) when hi - lo is finite and > 0, else 0 (one rounded subtraction, one correctly rounded
+ *   division); t = (x - lo) * scale, each operation rounded once, nothing fused; r = rintf(t) (ties to even);
+ *   q = r >= 65535 ? 65535 : (r > 0 ? r : 0), so a NaN gives 0.  A reader decodes lo + q * ((hi - lo) / 65535).  Velocities
+ *   and densities: float32 -> float16, round to nearest even, subnormal results and overflow to infinity as IEEE 754 has
+ *   them; a NaN keeps its sign and its ten top payload bits, 0x7c01 where those are zero (every bit pattern: numpy's
+ *   astype(float16)).
+ * The schedule: frame s is the state when dsl_stats.steps == s, before anything of step s, this step's sinks and emitters
+ *   included.  dsl_wcsph_step, dsl_pcisph_step and DSL_PCI_BEGIN_STEP capture it when s >= first_step,
+ *   (s - first_step) % every == 0 and fewer than max_frames frames were recorded (0: no limit): results do not depend on how
+ *   the steps were grouped into calls.
+ * The ring: `slots` frames of pinned host memory, each dsl_record_frame_bytes(spec, capacity) bytes (sources change N).  A
+ *   frame that finds no RELEASED slot is dropped whole and counted (DSL_OPT_RECORD_DROPPED); it does not count towards
+ *   max_frames.  Release is a host call, so what is dropped does not depend on timing.  Frames come out in FIFO order.
+ *
+ * dsl_recorder_set: stores the spec and allocates -- at most two staging frames in device memory (counted in
+ *   DSL_OPT_DEVICE_BYTES) and the pinned slots.  Blocking.  NULL: the recorder is off and everything is freed (unread frames
+ *   go with it).  A new spec replaces the old recorder and its frames.  DSL_ERR_INVALID (dsl_last_error names the field):
+ *   every, stride < 1, slots outside 1 .. 64, first_step or max_frames < 0, unknown field bits or encoding, and for
+ *   DSL_REC_Q16 without auto_box a box that is not finite or has box_min > box_max.  DSL_ERR_UNSUPPORTED: a slab handle (and
+ *   dsl_slab_config refuses while a recorder is set), after dsl_set_ids (host order is gone).  DSL_ERR_NOMEM when pinned or
+ *   device memory cannot be had: the handle stays usable, without a recorder.
+ * dsl_record_frame_bytes: the size of a frame of n_particles particles under the spec; 0 for a spec dsl_recorder_set would
+ *   refuse or n_particles < 1.
+ * dsl_record_now: one frame of the current state, between steps (its step field is dsl_stats.steps), for a host that drives
+ *   the passes itself.  It obeys the same ring (DSL_ERR_NOMEM when no slot is released) and counts towards max_frames
+ *   (DSL_ERR_INVALID once they are used up).  Asynchronous; like every entry point but the step drivers it settles a live
+ *   skin episode.
+ * dsl_record_poll: frames recorded so far, frames whose copy has landed and that are not yet released, frames dropped; any
+ *   pointer may be NULL.  Never blocks.  (dsl_sync waits for the copies on their way as well as for the steps.)
+ * dsl_record_peek: the oldest unreleased frame in its pinned slot and its size; waits for ITS copy only.  The pointer stays
+ *   valid and the bytes unchanged until dsl_record_release, which hands the slot back.  dsl_record_read: peek, memcpy into
+ *   host_out (bytes: its size, at least the frame's), release.  DSL_ERR_INVALID from the three with nothing to give, or for
+ *   a `bytes` that is too small.
+ *
+ * A refused call changes nothing.  While the caller's stream is being captured a step that would record returns
+ * DSL_ERR_UNSUPPORTED.  DSL_NEIGH_LSH_REF, boundary particles (never recorded), colliders, bodies and sources all work.  Not
+ * recorded: forces and pressures (held lazily), the extracted surface; no crop box; no recording on slab ranks.  With no
+ * recorder set: no launch, no allocation, no bit changes. */
+#define DSL_REC_VELOCITY 1 /* fields: positions always, | velocities | densities */
+#define DSL_REC_DENSITY 2
+enum { DSL_REC_F32 = 0, DSL_REC_Q16 = 1 };
+typedef struct dsl_recorder {
+  int32_t every;    /* >= 1: a frame at steps s >= first_step with (s - first_step) % every == 0 */
+  int32_t stride;   /* >= 1: host indices 0, stride, 2 stride, ... (dsl_download_decimated's) */
+  int32_t fields, encoding;
+  int32_t slots;    /* 1..64 frames of pinned host memory */
+  int32_t auto_box; /* Q16: 0 = box_min/box_max below, 1 = each frame's own bounds */
+  float box_min[3], box_max[3];
+  int64_t first_step; /* absolute, on dsl_stats.steps */
+  int64_t max_frames; /* 0: no limit */
+} dsl_recorder;
+int dsl_recorder_set(dsl_handle *h, const dsl_recorder *spec);
+size_t dsl_record_frame_bytes(const dsl_recorder *spec, int n_particles);
+int dsl_record_now(dsl_handle *h);
+int dsl_record_poll(dsl_handle *h, int64_t *recorded, int64_t *ready, int64_t *dropped);
+int dsl_record_peek(dsl_handle *h, const void **frame, size_t *bytes);
+int dsl_record_release(dsl_handle *h);
+int dsl_record_read(dsl_handle *h, void *host_out, size_t bytes);
+
 int dsl_get_stats(dsl_handle *h, dsl_stats *out);
 int dsl_sync(dsl_handle *h); /* Queue.Finish() pcisph_gpu_darwin.go:261,271 */
 
@@ -1123,8 +1206,14 @@ enum {
   DSL_OPT_EMITTED = 90,            /* (get) particles emitted so far, by the step drivers and by dsl_emit */
   DSL_OPT_EMIT_SKIPPED = 91,       /* (get) layers the step drivers skipped because they did not fit the capacity */
   DSL_OPT_REMOVED = 92,            /* (get) particles the sinks removed so far */
-  DSL_OPT_SINK_EVERY = 93          /* (set/get, default 8) the step drivers apply the sinks at steps s with s % every == 0;
+  DSL_OPT_SINK_EVERY = 93,         /* (set/get, default 8) the step drivers apply the sinks at steps s with s % every == 0;
                                       0: only dsl_particles_remove does.  Negative or above 2^30: DSL_ERR_INVALID */
+  /* the frame recorder (0 from all five while none is set) */
+  DSL_OPT_RECORD_FRAMES = 96,      /* (get) frames recorded so far, by the step drivers and by dsl_record_now */
+  DSL_OPT_RECORD_DROPPED = 97,     /* (get) frames dropped because no slot was released */
+  DSL_OPT_RECORD_READY = 98,       /* (get) unreleased frames whose copy has landed (never blocks) */
+  DSL_OPT_RECORD_PACK_MS = 99,     /* (get, blocking) milliseconds of the last frame's bounds + pack launches, as */
+  DSL_OPT_RECORD_COPY_MS = 100     /* DSL_OPT_SURFACE_COUNT_MS; of the last frame's copy to its pinned slot */
 };
 int dsl_set_option(dsl_handle *h, int option, double value);
 int dsl_get_option(dsl_handle *h, int option, double *value);
